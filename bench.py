@@ -11,10 +11,21 @@ layers), batch 2^20 per GPU, data-initialised weights (seed 0).  Batch rows are 
 so ranks shard the batch with no data-path collective besides that 8-byte all-reduce
 ("scaling": "weak": every rank evaluates its own 2^20 rows).
 
-One JSON line is printed by rank 0.  Besides the contract keys it carries
+One JSON line is printed by rank 0.  A plain run sets up, warms up, times the K steps and prints
+the line: the contract keys (metric, value, unit, higher_is_better, dtype, ms_per_step, ...) and
   roofline      the dominant libtfk kernel of the timed region: algorithmic bytes per launch
                 / its mean launch duration, measured with HIP events recorded on the launch
-                stream around every launch inside the timed region;
+                stream around every launch inside the timed region (no run of its own).
+
+    --dump-outputs DIR   after the timed steps, write what the last timed step returned to its
+                         caller as DIR/<name>.npy: log_prob (float32, rank 0's rows) and
+                         log_likelihood_sum (float64, all ranks).  The inputs are seeded, so two
+                         builds run with the same arguments can be compared output for output.
+    --full               everything else the benchmark measures, each in runs of its own after
+                         the timed steps: step_stats (per-step HIP-event times of further steps),
+                         roofline_layerwise, sample, train (with its child-process probes),
+                         configs (the other BASELINE configurations), trimmed by the --no-*
+                         switches, and
   cpu_baseline  the CPU oracle (oracle/, a C port of the reference's algorithm; the Python
                 reference cannot travel to the GPU box) timed on this host's cores on a
                 bounded sample of the same workload, rank 0 at N = 1 only;
@@ -364,6 +375,24 @@ def cpu_baseline_aten(flow_host, shape, batch_rows, target_seconds=8.0):
                       f"torch.set_num_threads({threads}), {dt:.1f} s"}
 
 
+DUMP_MAX_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, lp, total):
+    """--dump-outputs: what the last timed step handed to its caller, as <out_dir>/<name>.npy -- log_prob (float32, this
+    rank's rows in batch order) and log_likelihood_sum (float64, the all-reduced sum).  An output above the 64 MB
+    budget is written as a fixed, seeded sample of its rows, with the row indices beside it."""
+    os.makedirs(out_dir, exist_ok=True)
+    lp = lp.detach().reshape(-1)
+    if 4 * lp.numel() > DUMP_MAX_BYTES - (1 << 20):
+        keep = (DUMP_MAX_BYTES - (1 << 20)) // 12          # 4 bytes per value + 8 per row index
+        idx = np.sort(np.random.default_rng(1234).choice(lp.numel(), size=keep, replace=False))
+        lp = lp[torch.from_numpy(idx).to(lp.device)]
+        np.save(os.path.join(out_dir, "log_prob_rows.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "log_prob.npy"), lp.to(torch.float32).cpu().numpy())
+    np.save(os.path.join(out_dir, "log_likelihood_sum.npy"), total.detach().to(torch.float64).cpu().numpy().reshape(1))
+
+
 def spawn_ranks(n, argv):
     """`python bench.py --gpus N` with no launcher around it: start the N ranks as a CHILD process
     (python -m torch.distributed.run, one rank per GPU over RCCL), relay rank 0's JSON line on stdout and
@@ -513,8 +542,13 @@ def main():
                          "(config 4: --workload realnvp256 --total-rows 4194304 --gpus 8)")
     ap.add_argument("--priming", type=int, default=PRIMING_STEPS,
                     help="untimed steps before the requested warm-ups (clock ramp after idle; reported in the JSON)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every further leg (step_stats, layer-by-layer roofline, sample, train, cpu_baseline "
+                         "+ parity, the other configurations); a plain run times the K steps and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/log_prob.npy and DIR/log_likelihood_sum.npy")
     ap.add_argument("--stats-steps", type=int, default=100,
-                    help="extra steps, timed one by one with HIP events AFTER the K timed steps (median / min / max)")
+                    help="--full: extra steps, timed one by one with HIP events AFTER the K timed steps (median / min / max)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-fused", action="store_true",
                     help="layer-by-layer kernels + PyTorch-ROCm conditioner GEMMs (the split path)")
@@ -565,12 +599,12 @@ def main():
     rows = args.rows or rows
     if args.total_rows:
         rows = args.total_rows // world
-    flow_host = make_flow(arch, D, n_layers)
-    for layer in flow_host.bijection.modules():
+    flow_host = make_flow(arch, D, n_layers) if args.full else None      # the CPU legs' copy of the same model
+    flow = make_flow(arch, D, n_layers).to(dev)
+    for layer in flow.bijection.modules():
         seq = getattr(getattr(layer, "conditioner_transform", None), "sequential", None)
         if seq is not None and not isinstance(D, tuple):
             KernelTimer.true_hidden[D] = seq[0].out_features
-    flow = make_flow(arch, D, n_layers).to(dev)
     shape = D if isinstance(D, tuple) else (D,)
     DATA_BLOCK = 4096
     if args.total_rows and rows % DATA_BLOCK == 0:
@@ -626,10 +660,12 @@ def main():
             dist.barrier()
         elapsed = time.perf_counter() - t0
         timer.active = False
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, lp, total)        # now: later legs may reuse the buffers
         # distribution of the step time: stats_steps MORE steps (not part of `value`), each bracketed by its own
         # HIP events on the launch stream; the 8-byte all-reduces stay in flight as above
         step_ms = []
-        if args.stats_steps > 0:
+        if args.full and args.stats_steps > 0:
             marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.stats_steps + 1)]
             marks[0].record()
             for i in range(args.stats_steps):
@@ -800,7 +836,7 @@ def main():
                             "GBps": round(v["GBps"], 1)} for k, v in kernels.items()},
             "libtfk_ms_per_step": sum(v["ms"] for v in kernels.values()) / args.steps,
         }
-        if world == 1 and dom_name.startswith("flow_run"):
+        if args.full and world == 1 and dom_name.startswith("flow_run"):
             # the same workload layer by layer (one libtfk kernel per reference layer, conditioner
             # GEMMs on PyTorch-ROCm): its transform kernels are the HBM-bound ones, so their
             # roofline is reported next to the fused program's
@@ -832,7 +868,7 @@ def main():
                                 "hbm_frac": round(v["GBps"] / HBM_PEAK_GBS, 3)} for k, v in lw.items()},
                 "note": "same workload with TORCHFLOWS_AMD_FUSED=0 (bench.py --no-fused), 3 steps; `kernels` lists every "
                         "per-layer kernel's HBM fraction (affine_coupling[inplace] is the coupling transform pass)"}
-        if world == 1 and not args.no_sample:
+        if args.full and world == 1 and not args.no_sample:
             # sample throughput next to log_prob (Flow.sample = base draw +
             # bijection.inverse with log-det, flows.py:117-146), same rows, not part of `value`
             srows = step_rows
@@ -848,7 +884,7 @@ def main():
                                 "note": "Flow.sample((rows,), return_log_prob=True): torch.randn base "
                                         "draw + inverse flow program, 3 calls"}
             del xs, lps
-        if world == 1 and not args.no_train and not isinstance(D, tuple):
+        if args.full and world == 1 and not args.no_train and not isinstance(D, tuple):
             # one maximum-likelihood step on the HIP path = Flow.log_prob with
             # autograd (layer kernels, out of place) + reverse-mode kernels + conditioner GEMM
             # backward on PyTorch-ROCm + AdamW.  Not part of `value`.
@@ -986,7 +1022,7 @@ def main():
                     "bound": "hbm", "kernel": top, "achieved": bwd[top]["GBps"], "peak": HBM_PEAK_GBS,
                     "unit": "GB/s", "frac": bwd[top]["GBps"] / HBM_PEAK_GBS,
                     "bytes_per_launch": bwd[top]["bytes_per_launch"], "avg_us": bwd[top]["avg_us"]}
-        if world == 1 and not args.no_cpu_baseline and not isinstance(D, tuple):
+        if args.full and world == 1 and not args.no_cpu_baseline and not isinstance(D, tuple):
             base, ref = cpu_baseline(arch, D, n_layers, flow_host)
             result["cpu_baseline"] = base
             result["cpu_baseline_aten"] = cpu_baseline_aten(flow_host, (D,), 1 << 14)
@@ -996,7 +1032,7 @@ def main():
             err = np.max(d / np.maximum(1.0, np.abs(lp_ref)))
             result["parity"] = {"log_prob_max_rel_vs_oracle": float(err), "rows_checked": int(idx.numel()),
                                 "pass_rate_1e-5": float(np.mean(d <= 1e-5 * np.maximum(1.0, np.abs(lp_ref))))}
-        if world == 1 and not args.no_cpu_baseline and isinstance(D, tuple):
+        if args.full and world == 1 and not args.no_cpu_baseline and isinstance(D, tuple):
             # config 5: the oracle's C port covers the image LAYERS (masks, squeeze, 1x1 convolution), not the ConvNet
             # conditioner, so the CPU leg is this package's ATen path on the host cores and parity is taken against
             # the REFERENCE's own outputs for this model (tests/golden/flow_glow_3x32x32.npz, make_golden.py gen_glow32)
@@ -1015,7 +1051,7 @@ def main():
                                     "pass_rate_1e-5": float(np.mean(d <= 1e-5 * np.maximum(1.0, np.abs(fx["log_prob"])))),
                                     "note": "HIP path vs the reference's own log_prob of the config-5 model "
                                             "(seed-0 weights pinned by sha256, data-dependent state from the fixture)"}
-        if world == 1 and args.workload == "realnvp64" and not args.no_configs and not args.no_fused:
+        if args.full and world == 1 and args.workload == "realnvp64" and not args.no_configs and not args.no_fused:
             result["configs"] = {}
             for name in ("nsf64", "realnvp256", "glow32"):
                 t_leg = time.perf_counter()

@@ -1,5 +1,6 @@
 """bench.py prints ONE JSON line with the driver's contract fields (task statement, section 4): run on a
-reduced row count so the test stays short; the roofline / cpu_baseline objects must be present and sane."""
+reduced row count so the test stays short; the roofline / cpu_baseline objects (--full) must be present and sane.
+A plain run carries the headline figure alone and can write the last timed step's outputs (--dump-outputs)."""
 import json
 import os
 import subprocess
@@ -13,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_json_contract():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                          "--rows", "131072", "--no-sample", "--no-train"],
+                          "--rows", "131072", "--full", "--no-sample", "--no-train"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -51,6 +52,32 @@ def test_bench_json_contract():
     assert d["configs"]["glow32"]["libtfk_launches_per_step"] <= 4 * 60
     lw = d["roofline_layerwise"]["kernels"]
     assert "affine_coupling[inplace]" in lw and 0 < lw["affine_coupling[inplace]"]["hbm_frac"] <= 1.0
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain run (no --full) times its steps and nothing else: none of the further legs rides in the line, and
+    --dump-outputs writes the last timed step's log_prob (float32, one value per row) and its fp64 sum."""
+    import numpy as np
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                          "--rows", "8193", "--priming", "2", "--dump-outputs", str(tmp_path / "dump")],
+                         capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["dtype"] == "f32" and d["higher_is_better"] is True
+    assert d["metric"] == "log_prob evals/sec (RealNVP D=64)" and d["unit"] == "evals/s"
+    assert abs(d["value"] - 8193 * 2 / (d["ms_per_step"] * 2e-3)) / d["value"] < 1e-6
+    for key in ("cpu_baseline", "cpu_baseline_aten", "parity", "configs", "sample", "train", "roofline_layerwise"):
+        assert key not in d, key
+    assert d["step_stats"] is None
+    assert sorted(os.listdir(tmp_path / "dump")) == ["log_likelihood_sum.npy", "log_prob.npy"]
+    lp = np.load(tmp_path / "dump" / "log_prob.npy")
+    total = np.load(tmp_path / "dump" / "log_likelihood_sum.npy")
+    assert lp.dtype == np.float32 and lp.shape == (8193,) and np.isfinite(lp).all()
+    assert total.dtype == np.float64 and total.shape == (1,) and total[0] == d["log_likelihood_sum"]
+    # the sum is the fp64 sum of exactly these rows (fp64 accumulation of 8193 fp32 values: ~1e-12 relative)
+    assert abs(total[0] - lp.astype(np.float64).sum()) <= 1e-9 * abs(total[0])
 
 
 def test_bench_starts_its_own_ranks():

@@ -7,7 +7,7 @@ shift
 mkdir -p $OUT
 for V in base "$@"; do
   if [ "$V" == "base" ]; then unset TORCHFLOWS_AMD_LIB; else export TORCHFLOWS_AMD_LIB=$PWD/torchflows_amd/lib/variants/libtfk_$V.so; fi
-  timeout -k 10 200 python bench.py --no-cpu-baseline --no-sample --no-train --steps 50 --warmup 5 "${ARGS[@]}" > $OUT/$V.json 2> $OUT/$V.err || { echo "$V failed"; tail -3 $OUT/$V.err; exit 1; }
+  timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-sample --no-train --steps 50 --warmup 5 "${ARGS[@]}" > $OUT/$V.json 2> $OUT/$V.err || { echo "$V failed"; tail -3 $OUT/$V.err; exit 1; }
   python - <<PY
 import json
 d=json.load(open("$OUT/$V.json"))
