@@ -216,6 +216,15 @@ enum {
      * Op record field K = 256 (D = 64 only): GEMM 2 in the bf16 x 3 operand format described at TFK_OP_RQS_*_LEAN --
      * block A1 | b1 | A23[T2][2][64][4 dwords] | pre_s | pre_t, A23[t] = {[W_hi | W_mid], [W_lo | W_hi]}, b2 as the
      * weight of hidden unit 15 (hidden width <= 15).
+     * Op record field K = 512 (D = 32, 64, 128; gemm2_steps <= 3, hidden width H <= 10; resident operands, no context, even
+     * event sizes): GEMM 2 in the split-f16 operand format, ONE v_mfma_f32_16x16x32_f16 per tile -- every weight of W2 as
+     * hi = f16(w), lo = f16(w - hi) (after the pre-scalings above), the kernel splits the tanh outputs the same way and the
+     * three products W_hi h_hi + W_hi h_lo + W_lo h_hi of all units fill the K = 32 of the instruction.  Block
+     * A1 | b1 | A2h[T2][64][4 dwords] | b2[T2][4][4] | pre_s | pre_t.  The 16 M-rows of A1 / b1 hold, for lane group q =
+     * row >> 2, the hidden units 2 q, 2 q + 1, 8 + (q >> 1) and nothing (zeros) in rows 4 q .. 4 q + 3; A2h[t][lane] is eight
+     * f16, for the lane's row of tile t and its group q = lane >> 4: [Wh(2q) Wh(2q) Wl(2q) Wh(2q+1) | Wh(2q+1) Wl(2q+1) X Y]
+     * with (X, Y) = (Wh, Wh) of unit 8 + (q >> 1) in the even groups and (Wl, 0) in the odd ones; b2 stays the fp32
+     * accumulator initialiser.  Every op of a program carries the same K.
      * Bit 2 of src_plane (ABI v27, odd event sizes): HalfSplit then has one target more than sources and -- with the
      * reversals between the couplings -- the MIDDLE element is a target of EVERY coupling, so it has to sit in whichever
      * plane is being transformed: both planes reserve their last column (D/2 - 1 of the plane) for it, and a coupling whose

@@ -305,6 +305,123 @@ __device__ __forceinline__ void couple_lean3(const float *prm, int lane, int q, 
 }
 
 
+typedef _Float16 lf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 lf16x2 __attribute__((ext_vector_type(2)));
+
+// STEPS2 value that selects the split-f16 operand format below (0: bf16 x 3, 1..4: fp32 k-steps)
+constexpr int kStepsF16 = 16;
+
+// two fp32 values -> one dword of two f16, round to nearest even (v_cvt_pk_f16_f32)
+__device__ __forceinline__ int pack_f16(float lo_half, float hi_half)
+{
+    const cf32x2 v = {lo_half, hi_half};
+    return __builtin_bit_cast(int, __builtin_convertvector(v, lf16x2));
+}
+
+// The same coupling with GEMM 2 as ONE v_mfma_f32_16x16x32_f16 per tile ("split f16", hidden width <= 10).  The hidden
+// activations are tanh outputs in [-1, 1] and the weights host-side constants: each is held as an f16 pair
+// hi = f16(v), lo = f16(v - hi) (~2^-23 relative, <= 2^-25 absolute where lo goes subnormal), and the three piece products
+// W_hi h_hi + W_hi h_lo + W_lo h_hi of up to 10 hidden units fill the K = 32 of one MFMA (~16 cycles, and the vector ALU
+// stays free beside it) where the fp32 format takes ceil(H / 4) v_mfma_f32_16x16x4_f32 of 32 cycles each.
+//   * GEMM 1 is the fp32 one, but the host orders W1's 16 M-rows so that lane group q's accumulator registers 0, 1 are
+//     hidden units 2 q, 2 q + 1 and register 2 is unit 8 (groups 0, 1) or 9 (groups 2, 3); register 3 is dead (no tanh).
+//   * The lane's B-operand is the lane-uniform pattern [hi0 lo0 hi0 hi1 | lo1 hi1 hi2 lo2] of its three activations (13
+//     vector instructions, no cross-lane movement); the A-operand of row i in group q is
+//     [Wh(2q) Wh(2q) Wl(2q) Wh(2q+1) | Wh(2q+1) Wl(2q+1) X Y], (X, Y) = (Wh, Wh) of unit 8 in group 0, (Wl, 0) of unit 8 in
+//     group 1, and the same of unit 9 in groups 2, 3.
+//   * b2 stays the fp32 accumulator initialiser: exact, one ds_read_b128 per tile and no vector instruction (as the weight
+//     of a constant unit it would be rounded to two f16 pieces and exists only for H <= 9).
+//   * The tiles' MFMAs are issued side by side on independent accumulators, in groups of two (of four at D = 128).
+// Block: A1[EPL/4][64][4] | b1[4][4] | A2h[T2][64][4 dwords] | b2[T2][4][4] | pre_s[HALF] | pre_t[HALF]
+template <int EPL, int KIND, bool FAST>
+__device__ __forceinline__ void couple_lean_h(const float *prm, int lane, int q, const float (&src)[EPL],
+                                              float (&tgt)[EPL], float &ld2, float &umin)
+{
+    constexpr bool affine = KIND < 2;
+    constexpr int HALF = 4 * EPL;
+    constexpr int T2 = affine ? EPL / 2 : EPL / 4;
+    const cf32x4 *A1 = reinterpret_cast<const cf32x4 *>(prm);
+    const float *b1 = prm + EPL * 64;
+    const li32x4 *A2h = reinterpret_cast<const li32x4 *>(b1 + 16);
+    const float *b2 = b1 + 16 + T2 * 64 * 4;
+    const float *pre = b2 + T2 * 16;
+
+    cf32x4 acc = *reinterpret_cast<const cf32x4 *>(b1 + 4 * q);
+#pragma unroll
+    for (int g = 0; g < EPL / 4; ++g) {
+        const cf32x4 w = A1[g * 64 + lane];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w[k], src[4 * g + k], acc, 0, 0, 0);
+    }
+#pragma unroll
+    for (int i = 0; i < EPL / 4; ++i) {
+        const cf32x4 s = *reinterpret_cast<const cf32x4 *>(pre + EPL * q + 4 * i);
+        const cf32x4 t = *reinterpret_cast<const cf32x4 *>(pre + HALF + EPL * q + 4 * i);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) tgt[4 * i + k] = fmaf(s[k], tgt[4 * i + k], t[k]);
+    }
+    // Nothing is scheduled across this point: without it the compiler hoists the GEMM-2 operand loads of this coupling over
+    // the previous coupling's epilogue, and the D = 64 affine kernel needs 152 VGPRs (128 + 96 bytes of scratch when held
+    // to 4 waves per SIMD); with it 106 and no scratch.  GEMM 1 above still overlaps the previous epilogue.
+    __builtin_amdgcn_sched_barrier(0);
+    float hi[3], lo[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const float h = fmaf(-2.0f, __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(acc[r]) + 1.0f), 1.0f);
+        hi[r] = (float)(_Float16)h;
+        lo[r] = h - hi[r];
+    }
+    const li32x4 B = {pack_f16(hi[0], lo[0]), pack_f16(hi[0], hi[1]), pack_f16(lo[1], hi[1]), pack_f16(hi[2], lo[2])};
+
+    // (groups of four at D = 128, of two below: four tiles' operands and accumulators side by side are 36 registers)
+    constexpr int GMAX = EPL >= 16 ? 4 : 2;
+    constexpr int GTH = T2 < GMAX ? T2 : GMAX;
+    static_assert(T2 % GTH == 0, "tile groups");
+#pragma unroll
+    for (int g0 = 0; g0 < T2; g0 += GTH) {
+        cf32x4 o[GTH];
+        li32x4 a2[GTH];
+#pragma unroll
+        for (int tt = 0; tt < GTH; ++tt) {
+            a2[tt] = A2h[(g0 + tt) * 64 + lane];
+            o[tt] = *reinterpret_cast<const cf32x4 *>(b2 + ((g0 + tt) * 4 + q) * 4);
+        }
+#pragma unroll
+        for (int tt = 0; tt < GTH; ++tt)
+            o[tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(lf16x8, a2[tt]), __builtin_bit_cast(lf16x8, B), o[tt], 0, 0, 0);
+#pragma unroll
+        for (int tt = 0; tt < GTH; ++tt) {
+            const int t = g0 + tt;
+            if constexpr (affine) {
+                if constexpr (FAST && KIND == 1) {
+                    ld2 += log2_scales<true>(o[tt][0], o[tt][2], 0.0f, 0.0f, umin);
+#pragma unroll
+                    for (int i = 0; i < 2; ++i)
+                        tgt[2 * t + i] = (tgt[2 * t + i] - o[tt][2 * i + 1]) * __builtin_amdgcn_exp2f(-o[tt][2 * i]);
+                } else {
+                const float al[2] = {__builtin_amdgcn_exp2f(o[tt][0]) + kAffMinScale, __builtin_amdgcn_exp2f(o[tt][2]) + kAffMinScale};
+                ld2 += log2_scales<FAST>(o[tt][0], o[tt][2], al[0], al[1], umin);
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    const int e = 2 * t + i;
+                    if constexpr (KIND == 0) tgt[e] = fmaf(al[i], tgt[e], o[tt][2 * i + 1]);
+                    else tgt[e] = (tgt[e] - o[tt][2 * i + 1]) * __builtin_amdgcn_rcpf(al[i]);
+                }
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int e = 4 * t + i;
+                    if constexpr (KIND == 2) tgt[e] = tgt[e] + o[tt][i];
+                    else tgt[e] = tgt[e] - o[tt][i];
+                }
+            }
+        }
+    }
+}
+
+
 // MADE-based affine layer, parallel map (MaskedAutoregressiveBijection.forward, layers_base.py:201-206; MADE = two
 // masked linear layers, transforms.py:184-267, masks folded into the packed weights), in the lean form: the
 // conditioner reads BOTH planes as they are (pending elementwise layers folded into W1 / b1), every element of both
@@ -390,13 +507,14 @@ __device__ __forceinline__ void made_lean(const float *prm, int lane, int q, flo
     }
 }
 
-// one coupling in whichever operand format the kernel was instantiated for (STEPS2 = 0: bf16 x 3)
+// one coupling in whichever operand format the kernel was instantiated for (STEPS2 = 0: bf16 x 3, kStepsF16: split f16)
 template <int EPL, int STEPS2, int KIND, bool FAST, bool CTX = false>
 __device__ __forceinline__ void couple_fmt(const float *prm, int lane, int q, const float (&src)[EPL],
                                            float (&tgt)[EPL], float &ld2, float &umin,
                                            const float (&cx)[4] = {0.0f, 0.0f, 0.0f, 0.0f}, int cs = 0)
 {
     if constexpr (STEPS2 == 0) couple_lean3<EPL, KIND, FAST>(prm, lane, q, src, tgt, ld2, umin);
+    else if constexpr (STEPS2 == kStepsF16) couple_lean_h<EPL, KIND, FAST>(prm, lane, q, src, tgt, ld2, umin);
     else couple_lean<EPL, STEPS2, KIND, FAST, CTX>(prm, lane, q, src, tgt, ld2, umin, cx, cs);
 }
 
@@ -523,6 +641,8 @@ constexpr int chain_block_floats()
     constexpr int T2 = KIND < 2 ? EPL / 2 : (EPL + 3) / 4;
     if constexpr (STEPS2 == 0)                               // bf16 x 3 operands: A1 | b1 | A23[T2][2][64][4 dwords] | pre_s | pre_t
         return EPL * 64 + 16 + T2 * 2 * 64 * 4 + 8 * EPL;
+    if constexpr (STEPS2 == kStepsF16)                       // split f16 operands: A1 | b1 | A2h[T2][64][4 dwords] | b2 | pre_s | pre_t
+        return EPL * 64 + 16 + T2 * 64 * 4 + T2 * 16 + 8 * EPL;
     constexpr int NA2 = (T2 * STEPS2 + 3) & ~3;
     return EPL * 64 + 16 + NA2 * 64 + T2 * 16 + 8 * EPL;
 }
@@ -596,7 +716,7 @@ __device__ __forceinline__ void chain_layers_stream(float *buf0, const float *__
 
 template <int EPL, int BLOCK, int STEPS2, int KIND, bool STREAM = false, bool CTX = false, bool ODD = false>
 __global__ __launch_bounds__(BLOCK) TFK_CHAIN_ATTR
-__attribute__((amdgpu_waves_per_eu((EPL == 16 && BLOCK == 768) ? 3 : (((EPL == 16 && BLOCK == 1024) || (EPL == 8 && CTX)) ? 4 : 1)))) void k_flow_chain(
+__attribute__((amdgpu_waves_per_eu((EPL == 16 && BLOCK == 768) ? 3 : (((EPL == 16 && BLOCK == 1024) || (EPL == 8 && (CTX || STEPS2 == kStepsF16))) ? 4 : 1)))) void k_flow_chain(
     const float *__restrict__ x, float *z, float *logdet, const float *__restrict__ gauss_loc,
     const float *__restrict__ gauss_log_scale, float *logprob, long long N,
     const float *__restrict__ params, int n_params, ChainProg prog, int flags, int xw)
@@ -609,7 +729,8 @@ __attribute__((amdgpu_waves_per_eu((EPL == 16 && BLOCK == 768) ? 3 : (((EPL == 1
     // resident: the whole parameter block; streamed: two coupling blocks | the closing TFK_OP_EW_FMA block
     constexpr int LB = chain_block_floats<EPL, STEPS2, KIND>();
     static_assert(!STREAM || KIND < 4, "streamed operands: affine / shift couplings");
-    static_assert(!CTX || (KIND < 4 && STEPS2 != 0 && !STREAM), "context: affine / shift couplings, fp32 format, resident");
+    static_assert(!CTX || (KIND < 4 && STEPS2 != 0 && STEPS2 != kStepsF16 && !STREAM), "context: affine / shift couplings, fp32 format, resident");
+    static_assert(STEPS2 != kStepsF16 || (KIND < 4 && !STREAM && !ODD), "split f16 operands: affine / shift couplings, resident, even event sizes");
     float *ew_s = STREAM ? lds + kStreamBufs * LB : lds + (prog.ew_offset >= 0 ? prog.ew_offset : 0);
     if constexpr (STREAM) {
         if (prog.ew_offset >= 0)
@@ -894,6 +1015,21 @@ static int launch_chain_k(const float *x, float *z, float *logdet, const float *
                           float *logprob, int64_t N, const float *params, int n_params, const ChainProg &prog,
                           int steps2, int flags, int xw, hipStream_t s, const char *fn)
 {
+    if (steps2 == kStepsF16) {                               // split f16 operands: resident, no context, even event sizes
+        if ((size_t)n_params + 16 * EPL + 4 > 160 * 1024 / sizeof(float) || prog.context || prog.move_mask)
+            return fail(TFK_EINVAL, "%s: the split-f16 operand format of lean couplings keeps its operands resident and takes "
+                        "no context and no odd event size", fn);
+        if constexpr ((EPL == 4 || EPL == 8 || EPL == 16) && KIND < 4) {
+            constexpr int BIGH = (EPL == 16) ? 768 : 512;
+            const bool bigh = N >= (int64_t)cu_count() * 3 * 128;
+            if (bigh)
+                return launch_chain_b<EPL, BIGH, kStepsF16, KIND>(x, z, logdet, loc, log_scale, logprob, N, params, n_params, prog, flags, xw, s, fn);
+            return launch_chain_b<EPL, kBlock, kStepsF16, KIND>(x, z, logdet, loc, log_scale, logprob, N, params, n_params, prog, flags, xw, s, fn);
+        } else {
+            return fail(TFK_EINVAL, "%s: the split-f16 operand format of lean couplings is built for affine / shift chains at "
+                        "D = 32, 64 and 128", fn);
+        }
+    }
     // operands that do not fit the LDS beside each other are streamed (chain_layers_stream): D >= 128, fp32 format
     if ((size_t)n_params + 16 * EPL + 4 > 160 * 1024 / sizeof(float) || ((flags & 8) && EPL >= 16 && KIND < 4 && (steps2 != 0 || EPL == 32))) {
         if (prog.move_mask)

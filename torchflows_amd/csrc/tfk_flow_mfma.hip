@@ -182,7 +182,7 @@ static int run_chain(const float *x, float *z, float *logdet, const float *loc, 
     for (int i = 0; i < kChainSideOps; ++i) prog.pre_kind[i] = prog.post_kind[i] = prog.pre_off[i] = prog.post_off[i] = 0;
     int phase = 0;                                           // 0 before the couplings, 1 in them, 2 behind the closing EW_FMA
     int kind = -1, steps2 = 1;
-    bool fmt3 = false;
+    bool fmt3 = false, fmth = false;
     for (int i = 0; i < n_ops; ++i) {
         const int32_t *rec = ops + 8 * i;
         const int k = rec[0], st = rec[2], off = rec[3];
@@ -247,10 +247,15 @@ static int run_chain(const float *x, float *z, float *logdet, const float *loc, 
             const int T2 = (kind < 2) ? EPL / 2 : (EPL + 3) / 4;
             const int nA2 = (T2 * st + 3) & ~3;
             const bool f3 = rec[4] == 256;               // K field: 256 = bf16 x 3 operands (no b2, A23[T2][2][64][4])
-            if (prog.n_c == 0) fmt3 = f3;
-            else if (f3 != fmt3) return fail(TFK_EINVAL, "%s: op %d: the ops of a lean program share one operand format", fn, i);
-            if (f3 && context) return fail(TFK_EINVAL, "%s: op %d: context-conditioned lean couplings use fp32 operands", fn, i);
+            const bool fh = rec[4] == 512;               // 512 = split f16 operands (A2h[T2][64][4], b2 kept; hidden width <= 10)
+            if (prog.n_c == 0) { fmt3 = f3; fmth = fh; }
+            else if (f3 != fmt3 || fh != fmth) return fail(TFK_EINVAL, "%s: op %d: the ops of a lean program share one operand format", fn, i);
+            if ((f3 || fh) && context) return fail(TFK_EINVAL, "%s: op %d: context-conditioned lean couplings use fp32 operands", fn, i);
+            if (fh && (st > 3 || move_mid || (EPL != 4 && EPL != 8 && EPL != 16)))
+                return fail(TFK_EINVAL, "%s: op %d: split-f16 operands (K = 512): affine / shift couplings of at most 3 GEMM-2 steps "
+                            "(hidden width <= 10), D = 32, 64 or 128, even event sizes", fn, i);
             need = f3 ? (int64_t)EPL * 64 + 16 + (int64_t)T2 * 2 * 64 * 4 + 2 * HALF
+                 : fh ? (int64_t)EPL * 64 + 16 + (int64_t)T2 * 64 * 4 + (int64_t)T2 * 16 + 2 * HALF
                       : (int64_t)EPL * 64 + 16 + (int64_t)nA2 * 64 + (int64_t)T2 * 16 + 2 * HALF + (cs_want ? 256 : 0);
             if (move_mid) {
                 if (context) return fail(TFK_EINVAL, "%s: op %d: context programs do not move a middle element", fn, i);
@@ -266,6 +271,7 @@ static int run_chain(const float *x, float *z, float *logdet, const float *loc, 
     }
     if (kind < 0) kind = 2;
     if (fmt3) steps2 = 0;
+    if (fmth) steps2 = kStepsF16;
     if (EPL == 2) return flow_chain_launch_2(x, z, logdet, loc, log_scale, logprob, N, params, (int)n_params, prog, kind, steps2, flags, xw, s, fn);
     if (EPL == 4) return flow_chain_launch_4(x, z, logdet, loc, log_scale, logprob, N, params, (int)n_params, prog, kind, steps2, flags, xw, s, fn);
     if (EPL == 8) return flow_chain_launch_8(x, z, logdet, loc, log_scale, logprob, N, params, (int)n_params, prog, kind, steps2, flags, xw, s, fn);

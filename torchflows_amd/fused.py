@@ -675,11 +675,46 @@ def lean_bf16x3_enabled(Dp: int = 64) -> bool:
     return mode == "1" or (mode == "auto" and Dp == 256)
 
 
-def _pack_lean(lk: int, H: int, Dp: int, W1t, b1, W2p, b2p, pre_s, pre_t, bf16x3: bool = False, W1c=None) -> torch.Tensor:
+def lean_f16x2_enabled(Dp: int = 64) -> bool:
+    """Split-f16 operands for GEMM 2 of affine / shift chains of hidden width <= 10 (csrc/tfk_flow_chain.h: couple_lean_h;
+    TORCHFLOWS_AMD_DEBUG=lean_f16x2=0 / 1; default "auto"): every weight and every tanh output as hi = f16(v),
+    lo = f16(v - hi), the three piece products of a tile in ONE v_mfma_f32_16x16x32_f16 where the fp32 format takes
+    ceil(H / 4) v_mfma_f32_16x16x4_f32.  ``1`` turns it on wherever the format exists (Dp in 32 / 64 / 128, resident
+    operands, no context, even event size, H <= 10, every weight representable, ``lean_bf16x3`` not forced); ``auto``
+    where it was measured faster by more than three times the spread of the runs it replaces (round 5, same box, the
+    two libraries alternating, five plain ``bench.py`` runs each, per launch / per step):
+    D = 64:  ON  -- RealNVP-64, 2^20 rows: 250.5 us (249.0 .. 253.0) -> 195.2 us (193.2 .. 196.9), 267.7 -> 213.1 us per step
+             (3.92 -> 4.92e9 evals/s): 12 f32 MFMAs per wave-layer (384 matrix cycles) become 4 f16 ones (~64) + 13 vector
+             instructions for the split; 106 VGPRs, two 512-thread workgroups per CU as before.
+    D = 128: ON  -- RealNVP-128, 2^20 rows: 501.1 us (499.5 .. 502.1) -> 365.1 us (356.9 .. 367.3), 518.9 -> 382.9 us per step.
+    D = 32:  OFF unless forced -- RealNVP(32, 8), 2^20 rows: 121.6 us (119.0 .. 122.1) -> 116.2 us (115.3 .. 116.8): 5.4 us
+             against a bar of 9.3; that launch moves 268 MB in 116 us and is no longer bound by the matrix pipe.
+    Parity: log_prob within 3e-7 of the fp32 operand format and of the host's fp64 value (tests/test_gpu_lean_f16.py)."""
+    mode = debug_switch("lean_f16x2", "auto")
+    return mode == "1" or (mode == "auto" and Dp in _F16X2_AUTO)
+
+
+_F16X2_AUTO = (64, 128)    # row widths at which "auto" selects the split-f16 format
+
+
+def _f16_pieces(w: torch.Tensor):
+    """fp64 -> (hi, lo) float16 with hi + lo ~ w, and whether every element passes the representability check of the
+    split-f16 format: |w| <= 65 504 and hi + lo within 2^-22 relative or 2^-24 absolute of w."""
+    ok = bool((w.abs() <= 65504.0).all())
+    hi = w.clamp(-65504.0, 65504.0).to(torch.float16)
+    lo = (w - hi.double()).to(torch.float16)
+    err = (hi.double() + lo.double() - w).abs()
+    ok = ok and bool(((err <= 2.0 ** -22 * w.abs()) | (err <= 2.0 ** -24)).all())
+    return hi, lo, ok
+
+
+def _pack_lean(lk: int, H: int, Dp: int, W1t, b1, W2p, b2p, pre_s, pre_t, bf16x3: bool = False, W1c=None,
+               f16x2: bool = False) -> Optional[torch.Tensor]:
     """Parameter block of a lean coupling op (csrc/tfk_flow_chain.h): lane-major MFMA A-operands
     A1[EPL/4][64][4] | b1[4][4] | A2[nA2/4][64][4] | b2[T2][4][4] | pre_s[hp] | pre_t[hp], with W1 / b1 multiplied by
     2 log2(e) and (affine) the scale-logit rows of W2 / b2 by log2(e) / 2, b2 += c0 log2(e).  Inputs fp64, physical
-    order, the pending elementwise maps of the source plane already folded into W1t / b1."""
+    order, the pending elementwise maps of the source plane already folded into W1t / b1.
+    ``f16x2``: the split-f16 format (H <= 10), or None if a weight of W2 is not representable in it."""
     hp, EPL = Dp // 2, Dp // 8
     dev = W1t.device
     P = W2p.shape[1]
@@ -697,12 +732,45 @@ def _pack_lean(lk: int, H: int, Dp: int, W1t, b1, W2p, b2p, pre_s, pre_t, bf16x3
     lane = torch.arange(64, device=dev)
     ql, il = lane >> 4, lane & 15
     unit1 = 4 * (il & 3) + (il >> 2)
+    qq, rr = torch.meshgrid(torch.arange(4, device=dev), torch.arange(4, device=dev), indexing="ij")
+    q2, r2 = il >> 2, il & 3
+    if f16x2:
+        # split-f16 format (couple_lean_h): M-row 4 q + r of GEMM 1 = hidden unit 2 q + r (r < 2), 8 + (q >> 1) (r = 2: units 8
+        # and 9 are computed twice), none (r = 3) -- so that every lane group holds all pieces of "its" units
+        assert H <= 10 and EPL >= 4 and W1c is None
+        live = (r2 < 3).to(torch.float64)
+        unit_h = torch.where(r2 < 2, 2 * q2 + r2, 8 + (q2 >> 1))                       # (64,): unit of M-row il
+        A1 = torch.stack([W1pad[unit_h, EPL * ql + s] * live for s in range(EPL)])
+        A1 = A1.reshape(EPL // 4, 4, 64).permute(0, 2, 1)
+        b1m = b1pad[torch.where(rr < 2, 2 * qq + rr, 8 + (qq >> 1))] * (rr < 3).to(torch.float64)
+        T2 = EPL // 2 if P == 2 else EPL // 4
+        u0, u1, u2 = 2 * ql, 2 * ql + 1, 8 + (ql >> 1)
+        first = (ql & 1) == 0                        # unit 8 / 9: (W_hi, W_hi) in the even group, (W_lo, 0) in the odd one
+        A2h, b2m, ok = [], [], True
+        for t in range(T2):
+            if P == 2:
+                m_l, p_l = EPL * q2 + 2 * t + (r2 >> 1), r2 & 1
+                m_b, p_b = EPL * qq + 2 * t + (rr >> 1), rr & 1
+            else:
+                m_l, p_l = EPL * q2 + 4 * t + r2, torch.zeros_like(r2)
+                m_b, p_b = EPL * qq + 4 * t + rr, torch.zeros_like(rr)
+            hi, lo, ok_t = _f16_pieces(W2pad[m_l, p_l])                                # (64, 16): the lane's row of W2
+            ok = ok and ok_t
+            g = lambda v, u: v[lane, u]
+            zero = torch.zeros(64, dtype=torch.float16, device=dev)
+            # against the lane's B-operand [hi0 lo0 hi0 hi1 | lo1 hi1 hi2 lo2]
+            A2h.append(torch.stack([g(hi, u0), g(hi, u0), g(lo, u0), g(hi, u1), g(hi, u1), g(lo, u1),
+                                    torch.where(first, g(hi, u2), g(lo, u2)), torch.where(first, g(hi, u2), zero)], dim=1))
+            b2m.append(b2q[m_b, p_b])
+        if not ok:
+            return None
+        A2h = torch.stack(A2h).contiguous().view(torch.int32)                          # (T2, 64, 4 dwords)
+        return torch.cat([A1.reshape(-1).float(), b1m.reshape(-1).float(), A2h.reshape(-1).view(torch.float32),
+                          torch.stack(b2m).reshape(-1).float(), pre_s.float(), pre_t.float()])
     A1 = torch.stack([W1pad[unit1, EPL * ql + s] for s in range(EPL)])                 # (EPL, 64)
     VW = min(EPL, 4)                                                                   # (16-wide rows: A1[64][2])
     A1 = A1.reshape(EPL // VW, VW, 64).permute(0, 2, 1)                                # lane-major groups of 4 k-steps
-    qq, rr = torch.meshgrid(torch.arange(4, device=dev), torch.arange(4, device=dev), indexing="ij")
     b1m = b1pad[4 * rr + qq]                                                           # [q][r]
-    q2, r2 = il >> 2, il & 3
     T2 = EPL // 2 if P == 2 else (EPL + 3) // 4
     A2, b2m = [], []
     for t in range(T2):
@@ -942,7 +1010,7 @@ def _pack_lean_made(H: int, Dp: int, W1f, b1f, W2p, b2p, pre_s, pre_t) -> torch.
 
 
 def _compile_lean(composition, plan, device, D: int, Dp: int, pos: torch.Tensor, pos_in: torch.Tensor,
-                  context: bool = False, odd: bool = False, allow_aff3: bool = True):
+                  context: bool = False, odd: bool = False, allow_aff3: bool = True, allow_f16: bool = True):
     """The chain as LEAN flow programs (csrc/tfk_flow_chain.h), or None: elementwise layers with global parameters,
     folded reversals and affine / shift couplings of one kind and one hidden width <= 16 whose source plane
     alternates -- every RealNVP / NICE preset.  The elementwise layers are deferred: physical column c carries a
@@ -980,6 +1048,13 @@ def _compile_lean(composition, plan, device, D: int, Dp: int, pos: torch.Tensor,
     aff3 = allow_aff3 and lean_bf16x3_enabled(Dp) and not odd and ((Dp == 64 and 0 < n_couplings <= 13)
                                                     or (Dp == 256 and not context and stream_chain_enabled()))
     # (D = 256, round 4: the streamed chain takes the bf16 x 3 format too -- 42 KB per coupling, two blocks resident)
+    # split-f16 operands (lean_f16x2_enabled): resident blocks of ONE launch, no context, even event sizes, H <= 10, and only
+    # while lean_bf16x3 is left at "auto" (0 asks for fp32 operands, 1 for bf16 x 3); whatever does not fit -- a weight that
+    # is not representable, a chain that would need a second launch -- is packed again in the fp32 format
+    affh = (allow_f16 and lean_f16x2_enabled(Dp) and debug_switch("lean_bf16x3", "auto") == "auto" and not odd and not context
+            and Dp in (32, 64, 128))
+    fp32_again = lambda: _compile_lean(composition, plan, device, D, Dp, pos_arg, pos_in, context=context, odd=odd,
+                                       allow_aff3=allow_aff3, allow_f16=False)
     # (context) if a context-conditioned elementwise layer precedes the first coupling, every elementwise layer before
     # that coupling is an interpreter op of the launch in front of the chain (the inverse direction starts with a
     # constant ActNorm followed by the context-conditioned layer)
@@ -1186,10 +1261,15 @@ def _compile_lean(composition, plan, device, D: int, Dp: int, pos: torch.Tensor,
                     items.append((OP_RQS_FWD_LEAN + lk - 4, plane | moved, steps2, block, extra))
                 else:
                     use3 = aff3 and H <= 15 and not context
-                    if items and bool(items[-1][4]) != use3:
-                        return None
-                    block = _pack_lean(lk, H, Dp, W1f, b1f, W2p, b2p, s[tgt].clone(), t[tgt].clone(), bf16x3=use3, W1c=W1c)
-                    items.append((OP_AFFINE_FWD_LEAN + lk, plane | moved, steps2, block, (256,) if use3 else ()))
+                    useh = affh and not use3 and H <= 10
+                    extra = (256,) if use3 else ((512,) if useh else ())
+                    if items and items[-1][4] != extra:
+                        return fp32_again() if affh else None
+                    block = _pack_lean(lk, H, Dp, W1f, b1f, W2p, b2p, s[tgt].clone(), t[tgt].clone(), bf16x3=use3, W1c=W1c,
+                                       f16x2=useh)
+                    if block is None:                         # (a weight the split-f16 format cannot hold)
+                        return fp32_again()
+                    items.append((OP_AFFINE_FWD_LEAN + lk, plane | moved, steps2, block, extra))
                 s[tgt] = 1.0
                 t[tgt] = 0.0
             else:
@@ -1243,6 +1323,8 @@ def _compile_lean(composition, plan, device, D: int, Dp: int, pos: torch.Tensor,
         blocks.append(block)
         used += n
     segments.append(Segment(ops, torch.cat(blocks).contiguous(), True))
+    if len(segments) > 1 and any(extra == (512,) for *_, extra in items):
+        return fp32_again()                              # (split-f16 blocks are a little larger: never at the price of a launch)
 
     def small_segment(its):                              # a few interpreter ops (elementwise layers) as one launch
         o, b, u = [], [], 0
