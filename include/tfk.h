@@ -368,6 +368,27 @@ int tfk_flow_run_mfma_in(const float *x, int32_t x_width, float *z, float *logde
                          const int32_t *ops, int32_t n_ops, const float *params, int64_t n_params,
                          int32_t accumulate, void *stream);
 
+/* ---- wide-row chain kernel: event sizes above 256 (additive to ABI v29) ----------------
+ * Chains of affine / shift HalfSplit couplings on EVEN event sizes 256 < D <= 2048, conditioner hidden width H <= 16, as ONE
+ * launch (csrc/tfk_flow_wide.h; packed by torchflows_amd/fused_wide.py).  A workgroup of 4 waves holds 16 rows for the
+ * whole chain; each half of the row (plane) is padded IN REGISTERS to hp = the next multiple of 64 above D / 2.  x and z
+ * are distinct (N, D) buffers at the logical width -- no padded copy on the way in or out -- and need no more than 4-byte
+ * alignment (16-byte accesses are used when D % 8 == 0 and both are 16-byte aligned).  z / logdet / logprob may be null.
+ * ops (HOST pointer): n_ops x int32[8] = {kind, src_plane, H, param_offset, 0, 0, 0, 0}: 1..64 couplings of ONE kind
+ *   (TFK_OP_AFFINE_*_LEAN / TFK_OP_SHIFT_*_LEAN; src_plane 0: the first half feeds the conditioner), then one TFK_OP_EW_FMA.
+ * params: per coupling  A1[4][hp/64][64][4] | b1[4][4] | A2[4][T2][64][4] | b2[4][T2][4][4] | pre_s[hp] | pre_t[hp]
+ *   (T2 = hp/32 affine, hp/64 shift; lane-major MFMA A-operands per wave, pre-scaled as in the lean format -- the layout is
+ *   spelled out at the top of csrc/tfk_flow_wide.h); the TFK_OP_EW_FMA block is s[2 hp] | t[2 hp] | logdet_const | pad[3].
+ * gauss_loc / gauss_log_scale (with logprob): 2 hp entries in the kernel's column order, plane A then plane B; pad columns
+ *   loc 0 and log_scale -0.5 log(2 pi).
+ * flags: bit 0 = add to logdet instead of overwriting it; bit 1 = store the rows reversed (z[n, D-1-c] = column c);
+ *   bit 2 = logprob is the base density of the rows as they come IN plus the log-det (Flow.sample with return_log_prob).
+ * Rows past N in the last tile are computed on zeros and not stored. */
+int tfk_flow_wide_supported(int32_t D, int32_t H);   /* even D, 256 < D <= 2048, 1 <= H <= 16 */
+int tfk_flow_run_wide(const float *x, float *z, float *logdet, const float *gauss_loc, const float *gauss_log_scale,
+                      float *logprob, int64_t N, int32_t D, const int32_t *ops, int32_t n_ops,
+                      const float *params, int64_t n_params, int32_t flags, void *stream);
+
 /* Linear rational spline coupling: MonotonicSpline + LinearRational
  * (spline/base.py:53-72, spline/linear_rational.py:9-182) inside CouplingBijection.forward / inverse.
  * Same conventions as tfk_rqs_coupling_*; h is (N, T, 4*n_bins) = [u_x | u_y | u_lambda | u_d (K-1) |

@@ -81,6 +81,7 @@ class Segment:
     ops: List[tuple]                          # (kind, src_plane, H, offset[, K, boundary, scale, c])
     params: torch.Tensor                      # fp32 device block, numel % 4 == 0
     mfma: bool = False                        # packed for tfk_flow_run_mfma (matrix-core conditioner)
+    wide: bool = False                        # packed for tfk_flow_run_wide (event sizes above 256, fused_wide.py)
 
     def packed_ops(self):
         """The op records as the ctypes array the C-ABI takes, built once per segment."""
@@ -1359,6 +1360,16 @@ def compile_chain(composition, direction: int, device: torch.device,
     Dp = D
     if not native.lib().tfk_flow_mfma_supported(D) and D % 2 == 0 and 4 <= D < 256:
         Dp = 64 if D < 64 else (128 if D < 128 else 256)
+    # even event sizes above 256: the wide-row chain kernel (csrc/tfk_flow_wide.h), one launch for the chain -- tried first,
+    # so that D = 512 only falls to the vector-ALU interpreter with TORCHFLOWS_AMD_MFMA=0 or TORCHFLOWS_AMD_DEBUG=wide=0
+    if mfma is None and mfma_enabled() and not context and D % 2 == 0 and D > 256:
+        from torchflows_amd import fused_wide
+        if fused_wide.enabled():
+            order_w = composition.layers if direction == FORWARD else list(composition.layers)[::-1]
+            chain = fused_wide.compile_wide(composition, _flatten(order_w, "forward" if direction == FORWARD else "inverse"),
+                                            device, D, direction)
+            if chain is not None:
+                return chain
     # odd event sizes: HalfSplit moves one element across the halves at every reversal, so every element gets
     # its own index in both planes (plane width >= D) and changes planes by TFK_OP_PLANE_SWAP
     slots = D % 2 == 1 and 3 <= D <= 64          # (the swap op is not built for 256-wide rows)
@@ -1510,7 +1521,7 @@ def padded_enabled(D: int, Dp: int) -> bool:
 def sample_ready(chain: Optional[CompiledChain]) -> bool:
     """One matrix-core launch: the base density of the incoming rows can ride along (flag bit 2)."""
     return (chain is not None and len(chain.segments) == 1 and chain.segments[0].mfma
-            and chain.pos_in is None)
+            and (chain.pos_in is None or chain.segments[0].wide))
 
 
 def invalidate(module: nn.Module, compiled_only: bool = False) -> None:
@@ -1692,8 +1703,14 @@ def _why_declined(composition, direction: int) -> str:
     plan = _flatten(order, "forward" if direction == FORWARD else "inverse")
     if plan is None:
         return "a layer's forward / inverse is not one of this package's implementations"
-    if not (3 <= D <= 512):
-        return f"event size {D} is outside the supported range"
+    # what the kernels back: every event size 3 .. 256 (chain kernels / interpreters, padded where needed), above that
+    # EVEN sizes up to 2048 for affine / shift coupling chains with hidden width <= 16 and no context (the wide-row chain
+    # kernel, tfk_flow_run_wide), and 512 on the vector-ALU interpreter
+    if D < 3 or D > 2048:
+        return f"event size {D} is outside the supported range (3 .. 256, and even sizes up to 2048 for affine / shift couplings)"
+    if D > 256 and D % 2 == 1:
+        return f"event size {D} is odd: above 256 only even event sizes have a flow-program kernel"
+    wide_only = D > 256 and D != 512
     for layer, _ in plan:
         if isinstance(layer, PermutationMatrix):
             continue
@@ -1704,11 +1721,21 @@ def _why_declined(composition, direction: int) -> str:
                     f"conditioner {type(ct).__name__}")
             if layer.context_shape is not None:
                 if type(ct).__name__ != "FeedForward" or D > 256:
-                    return what + f", context_shape {tuple(layer.context_shape)})"
+                    return what + f", context_shape {tuple(layer.context_shape)}" + (
+                        f": no context-conditioned flow program above event size 256)" if D > 256 else ")")
             seq = getattr(ct, "sequential", None)
             hidden = getattr(seq[0], "out_features", None) if seq is not None and len(seq) else None
             kind = layer.transformer.native_kind
             plain = type(ct).__name__ in ("FeedForward", "MADE") and hidden is not None
+            if wide_only:
+                if type(ct).__name__ == "FeedForward" and hidden is not None and hidden <= 16 \
+                        and kind in ("affine", "inverse_affine", "shift"):
+                    continue
+                if type(ct).__name__ == "FeedForward" and hidden is not None and kind in ("affine", "inverse_affine", "shift"):
+                    return what + f", hidden width {hidden} > 16 at event size {D}: the wide-row chain kernel holds one " \
+                                  f"16-unit hidden tile)"
+                return what + (f", hidden width {hidden}" if hidden else "") + \
+                    f", event size {D}: above 256 only affine / shift couplings with a FeedForward conditioner run fused)"
             if plain and kind in ("affine", "inverse_affine", "shift") and hidden <= 128:
                 continue
             if plain and kind == "rqs" and hidden <= 16 and getattr(layer.transformer, "n_bins", 8) == 8 and D <= 128:
@@ -1739,7 +1766,7 @@ def sum_ready(chain: Optional[CompiledChain]) -> bool:
     of a 261 us step) and adds ~6 us to the kernel (one agent-scope ticket per workgroup, 3 072 of them): 263.7 against
     261.2 us per step over 20 steps, 239.3 against 241.3 us at the median of 100 -- a wash."""
     return (chain is not None and len(chain.segments) == 1 and chain.segments[0].mfma
-            and chain.segments[0].ops[0][0] in _LEAN_KINDS
+            and chain.segments[0].ops[0][0] in _LEAN_KINDS and not chain.segments[0].wide
             and debug_switch("sum_in_kernel", "0") == "1")
 
 
@@ -1753,6 +1780,10 @@ def run_chain(chain: CompiledChain, rows: torch.Tensor, want_rows: bool, base=No
     ``sum_out`` (1-element float64, ``sum_ready`` chains with ``base``): receives the fp64 sum of the log-probabilities
     from the same launch."""
     assert sum_out is None or (sum_ready(chain) and base is not None and not base_of_input and context is None)
+    if chain.segments and chain.segments[0].wide:           # event sizes above 256: one tfk_flow_run_wide launch
+        from torchflows_amd import fused_wide
+        assert context is None
+        return fused_wide.run_wide(chain, rows, want_rows, base=base, base_of_input=base_of_input)
     if context is not None and chain.ctx_width is not None and (context.dim() != 2 or context.shape[1] != chain.ctx_width):
         # the kernels only count 4-wide k-steps: a context of another width would be truncated or zero-padded in
         # silence where the reference's Linear layer raises a shape error (conditioning/context.py:46-60)

@@ -35,6 +35,7 @@ SYMBOLS = (
     "tfk_flow_supported", "tfk_flow_run",
     "tfk_flow_mfma_supported", "tfk_flow_lean_supported", "tfk_flow_run_mfma", "tfk_flow_run_mfma_in", "tfk_flow_run_mfma_ctx",
     "tfk_flow_sum_workspace_bytes", "tfk_flow_run_mfma_sum",
+    "tfk_flow_wide_supported", "tfk_flow_run_wide",
     "tfk_affine_coupling_bwd", "tfk_shift_coupling_bwd",
     "tfk_rqs_coupling_bwd_supported", "tfk_rqs_coupling_bwd", "tfk_lrs_coupling_bwd",
     "tfk_elementwise_affine_bwd_workspace_bytes", "tfk_elementwise_affine_bwd",
@@ -147,6 +148,8 @@ def _bind(L: C.CDLL) -> None:
     L.tfk_flow_sum_workspace_bytes.argtypes = []
     L.tfk_flow_sum_workspace_bytes.restype = _i64
     L.tfk_flow_run_mfma_sum.argtypes = [_vp, _i32] + L.tfk_flow_run.argtypes[1:-1] + [_vp, _vp, _vp]
+    L.tfk_flow_wide_supported.argtypes = [_i32, _i32]
+    L.tfk_flow_run_wide.argtypes = L.tfk_flow_run.argtypes
     L.tfk_affine_coupling_bwd.argtypes = [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _vp]
     L.tfk_shift_coupling_bwd.argtypes = [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _vp]
     L.tfk_rqs_coupling_bwd_supported.argtypes = [_i32]
@@ -1154,6 +1157,29 @@ def flow_run_mfma(x, z, logdet, gauss_loc, gauss_log_scale, logprob, ops, params
             (1 if accumulate else 0) | (2 if reverse_out else 0) | (4 if base_of_input else 0) | _stream_flag())
     with _device_guard(x):
         rc = lib().tfk_flow_run_mfma(*args, _stream(x))
+    calls += 1
+    _check(rc, name)
+
+
+def flow_run_wide(x, z, logdet, gauss_loc, gauss_log_scale, logprob, ops, params, accumulate=False,
+                  reverse_out=False, base_of_input=False):
+    """Chain of affine / shift couplings on an even event size in (256, 2048] as one launch (tfk_flow_run_wide).
+    x / z (N, D) at the logical width; ops and params packed by fused_wide.compile_wide; gauss_loc / gauss_log_scale in the
+    kernel's column order (2 x the padded plane width).  z / logdet / logprob may be None."""
+    global calls
+    name = "tfk_flow_run_wide"
+    N, D = _rows(x, name)
+    hp2 = 2 * ((D // 2 + 63) // 64 * 64)
+    ops_arr = _pack_ops(ops)
+    for t, n in ((z, N * D), (logdet, N), (logprob, N), (gauss_loc, hp2), (gauss_log_scale, hp2)):
+        if t is not None and t.numel() != n:
+            raise NativeError(f"{name}: tensor with {t.numel()} elements, expected {n}")
+    args = (_f32(x, name), _f32(z, name), _f32(logdet, name), _f32(gauss_loc, name),
+            _f32(gauss_log_scale, name), _f32(logprob, name), N, D, ops_arr, _n_ops(ops),
+            _f32(params, name), params.numel(),
+            (1 if accumulate else 0) | (2 if reverse_out else 0) | (4 if base_of_input else 0))
+    with _device_guard(x):
+        rc = lib().tfk_flow_run_wide(*args, _stream(x))
     calls += 1
     _check(rc, name)
 
