@@ -736,14 +736,42 @@ int tfk_rqs_coupling_train_bwd_hid(const float *x, float *g, const float *gld, c
  * ROWS (dW2 = dL/dh^T hidden with A = gh_perm, M = 768; dW1^T = x_A^T dL/dpre with A = x, lda = D, M = 32; db1 with
  * A = gpre_perm, M = 16, column 15 of B == 1) on v_mfma_f32_16x16x4_f32, deterministic (per-workgroup partial blocks
  * added in a fixed order), with no GEMM-library call -- what makes the spline training step capturable into a hipGraph.
- * A (N, lda) row-major, only its first M columns are read; M = 16, 32 or a multiple of 256 (<= 1024); B (N, 16).
+ * A (N, lda) row-major, only its first M columns are read; M = 16, 32 or a multiple of 64 (<= 2048; multiples of 256 up
+ * to 1024 run 256 columns per workgroup, the others 64); B (N, 16).
  * out holds M * 16 floats in ACCUMULATOR order: tile t (16 columns of A), lane (q, j), register r ->
  *   out[(t * 64 + 16 q + j) * 4 + r] = sum_n A[n][col(t, 4 q + r)] * B[n][j],
- *   col(t, i) = 64 (t >> 2) + 4 i + (t & 3) for M >= 256, 16 t + i for M = 16 / 32.
+ *   col(t, i) = 64 (t >> 2) + 4 i + (t & 3) for M >= 64, 16 t + i for M = 16 / 32.
  * workspace: tfk_rows_outer_workspace_bytes(M) bytes. */
 int64_t tfk_rows_outer_workspace_bytes(int32_t M);
 int tfk_rows_outer(const float *A, int32_t lda, int32_t M, const float *B, float *out, float *workspace,
                    int64_t N, void *stream);
+
+/* ---- training above 256 columns: reverse mode of ONE wide coupling (additive to ABI v29) ----------------
+ * The layer of tfk_affine_coupling_train_bwd (HalfSplit affine / shift coupling, FeedForward(Linear, Tanh, Linear)
+ * conditioner, hidden width H <= 15) on event sizes 256 < D <= 1024, D % 8 == 0, with the row spread over the four waves
+ * of a workgroup as in tfk_flow_run_wide (csrc/tfk_wide_bwd.h): conditioner re-evaluation, transform backward, dL/dhidden
+ * and dL/dx_source in one launch.  x, g, gld, inverse_form, gscale (D floats or NULL), g_reversed as in
+ * tfk_affine_coupling_train_bwd; shift != 0: a Shift coupling (no scale logit; inverse_form: out = x - h).
+ * The sums over the batch rows are NOT taken here: the launch writes three records, and tfk_rows_outer contracts them
+ * (hp = the next multiple of 64 above D / 2, the plane width of the wide kernels):
+ *   gh_rec   (N, 2 hp): column 2 c + p = dL/d(parameter p -- 0 scale logit, 1 shift -- of target column c), with respect to
+ *            the module's own conditioner outputs; shift couplings: (N, hp), column c.  Columns of c >= D / 2 are padding
+ *   gpre_rec (N, 16):   column 4 q + r = dL/d(pre-activation of hidden unit 4 r + q)
+ *   hid_rec  (N, 16):   column 4 q + r = tanh(pre-activation of hidden unit 4 r + q), column 15 == 1 (the bias column)
+ * so that  dW2 | db2 = rows_outer(gh_rec, M = 2 hp (hp), hid_rec),  dW1 = rows_outer(x, lda = D, M = hp, gpre_rec) (columns
+ * >= D / 2 are target elements: not mapped back),  db1 = rows_outer(gpre_rec, M = 16, hid_rec) column 15.
+ * params: tfk_wide_coupling_train_bwd_param_floats(D, shift) floats -- the forward block tfk_flow_run_wide reads for this
+ *   coupling (pre-scaled as there), then A2T[4][T2][64][4] | A1T[4][hp/64][64][4] in the module's own scale (layout at the
+ *   top of csrc/tfk_wide_bwd.h; packed by torchflows_amd/autograd.py:_WideTrainPack).
+ * tfk_wide_coupling_train_bwd_grid_cap: the most workgroups (tiles of 16 rows in flight) a launch uses; above it the
+ *   workgroups loop over the tiles.
+ * Rows past N in the last tile are computed on zeros; neither their g nor their record rows are written. */
+int tfk_wide_coupling_train_bwd_supported(int32_t D, int32_t H);   /* D % 8 == 0, 256 < D <= 1024, 1 <= H <= 15 */
+int64_t tfk_wide_coupling_train_bwd_param_floats(int32_t D, int32_t shift);
+int64_t tfk_wide_coupling_train_bwd_grid_cap(int32_t D, int32_t shift);
+int tfk_wide_coupling_train_bwd(const float *x, float *g, const float *gld, const float *params, int64_t n_params,
+                                float *gh_rec, float *gpre_rec, float *hid_rec, int64_t N, int32_t D, int32_t shift,
+                                int32_t inverse_form, const float *gscale, int32_t g_reversed, void *stream);
 
 #ifdef __cplusplus
 }

@@ -13,6 +13,11 @@ bijections/base.py:203-224).  Here a whole composition is ONE ``torch.autograd.F
   ("recompute, not store").  The conditioner MLP's own backward (two skinny GEMMs) is
   ``torch.autograd.grad`` on PyTorch-ROCm, fed with the kernel's ``dL/dh``.
 
+Affine / shift couplings with the plain Linear-Tanh-Linear conditioner skip even that: at 64 / 128 / 256 columns the whole
+layer backward is one launch (``_TrainPack``), above 256 columns (D % 8 == 0 up to 1024) one launch plus three
+``tfk_rows_outer`` products (``_WideTrainPack``, csrc/tfk_wide_bwd.h) -- no GEMM-library call, so ``Flow.fit`` can capture
+the step.
+
 Only what the kernels cover takes this route (affine / inverse-affine / shift / RQ-spline
 couplings with 4, 8 or 16 bins, ElementwiseAffine / ActNorm, permutations, no context);
 anything else keeps the ATen composite graph.  ``TORCHFLOWS_AMD_TRAIN=0`` forces the latter.
@@ -399,6 +404,220 @@ class _RqsTrainPack:
         return flat[self.param_index]
 
 
+class _WideTrainPack:
+    """Index maps between a coupling layer's [W1 | b1 | W2 | b2 | 0] and the layouts of the wide training launches (event
+    sizes 256 < D <= 1024, D % 8 == 0), built once per (D, H, device, shift):
+
+    (a) ``fwd_index`` / ``fwd_mul`` / ``fwd_add``: the operand block ``tfk_flow_run_wide`` reads for a one-coupling program
+        (csrc/tfk_flow_wide.h; ``fused_wide.pack_coupling`` with pre_s = 1, pre_t = 0) as ONE gather and ONE multiply-add in
+        float64 -- the lean pre-scaling (W1 / b1 times 2 log2 e, the logit rows times log2(e) / 2, + c0 log2 e) --, so the
+        block is bit for bit the inference packer's;
+    (b) behind it, in the module's own scale, the transposed operands A2T | A1T of ``tfk_wide_coupling_train_bwd``
+        (csrc/tfk_wide_bwd.h): ``param_index`` = (a) + (b), ``n_bwd`` floats -- the head of a layer's packed block; the
+        closing TFK_OP_EW_FMA block (4 hp + 4 floats) follows at offset ``n_bwd``;
+    (c) ``acc_index``: from the three ``tfk_rows_outer`` outputs [gh_rec^T hid_rec (GH x 16) | x^T gpre_rec (hp x 16) |
+        gpre_rec^T hid_rec (16 x 16)], accumulator order (include/tfk.h), to [dW1 (H, D/2) | db1 (H) | dW2 (TP, H) | db2 (TP)].
+    Pad columns (D / 2 <= c < hp) and hidden units >= H read the appended zero; their accumulators are never mapped back.
+    The record buffers and the accumulator block live here: nothing is allocated per step."""
+
+    _cache = {}
+
+    @classmethod
+    def get(cls, D: int, H: int, device, shift: bool = False) -> "_WideTrainPack":
+        key = (D, H, str(device), shift)
+        if key not in cls._cache:
+            cls._cache[key] = cls(D, H, device, shift)
+        return cls._cache[key]
+
+    def __init__(self, D: int, H: int, device, shift: bool = False):
+        from torchflows_amd import fused
+        half = D // 2
+        hp = (half + 63) // 64 * 64
+        E = hp // 16
+        P = 1 if shift else 2
+        T2, G1 = (E // 4 if shift else E // 2), E // 4
+        TP = P * half
+        self.D, self.H, self.hp, self.E, self.shift, self.device = D, H, hp, E, shift, device
+        off_b1 = H * half
+        off_W2 = off_b1 + H
+        off_b2 = off_W2 + TP * H
+        Z = off_b2 + TP                                   # index of the appended zero
+        self.n_flat = Z + 1
+        ar = torch.arange
+        W1idx = torch.full((16, hp), Z, dtype=torch.long)
+        W1idx[:H, :half] = ar(H)[:, None] * half + ar(half)[None, :]
+        b1idx = torch.full((16,), Z, dtype=torch.long)
+        b1idx[:H] = off_b1 + ar(H)
+        W2idx = torch.full((hp, P, 16), Z, dtype=torch.long)
+        W2idx[:half, :, :H] = off_W2 + ((ar(half)[:, None, None] * P + ar(P)[None, :, None]) * H + ar(H)[None, None, :])
+        b2idx = torch.full((hp, P), Z, dtype=torch.long)
+        b2idx[:half] = off_b2 + ar(half)[:, None] * P + ar(P)[None, :]
+        lane = ar(64)
+        ql, il = lane >> 4, lane & 15
+        unit1 = 4 * (il & 3) + (il >> 2)
+        q2, r2 = il >> 2, il & 3
+        w_, k_ = ar(4), ar(4)
+        qq, rr = torch.meshgrid(ar(4), ar(4), indexing="ij")
+        g_ = ar(G1)
+        t_ = ar(T2)
+        # A1[w][g][l][k]: hidden unit unit1(i), source column (4 w + q) E + 4 g + k
+        cols = (4 * w_.view(4, 1, 1, 1) + ql.view(1, 1, 64, 1)) * E + 4 * g_.view(1, -1, 1, 1) + k_.view(1, 1, 1, 4)
+        A1 = W1idx[unit1.view(1, 1, 64, 1).expand_as(cols), cols]
+        b1m = b1idx[4 * rr + qq]                          # [q][r]
+        # output row i = 4 q2 + r of GEMM-2 tile t of wave w: (target column, parameter)
+        if shift:
+            col_of = lambda qv, rv: (4 * w_.view(4, 1, 1, 1) + qv) * E + 4 * t_.view(1, -1, 1, 1) + rv
+            par_of = lambda rv: torch.zeros_like(rv)
+        else:
+            col_of = lambda qv, rv: (4 * w_.view(4, 1, 1, 1) + qv) * E + 2 * t_.view(1, -1, 1, 1) + (rv >> 1)
+            par_of = lambda rv: rv & 1
+        shape = (4, T2, 64, 4)
+        # A2[w][t][l][k]: hidden unit 4 k + (l >> 4) for output row i = l & 15
+        m_l = col_of(q2.view(1, 1, 64, 1), r2.view(1, 1, 64, 1)).expand(shape)
+        p_l = par_of(r2).view(1, 1, 64, 1).expand(shape)
+        A2 = W2idx[m_l, p_l, (4 * k_.view(1, 1, 1, 4) + ql.view(1, 1, 64, 1)).expand(shape)]
+        m_b = col_of(qq.view(1, 1, 4, 4), rr.view(1, 1, 4, 4)).expand(4, T2, 4, 4)
+        p_b = par_of(rr).view(1, 1, 4, 4).expand(4, T2, 4, 4)
+        b2m = b2idx[m_b, p_b]                             # [w][t][q][r]
+        # A2T[w][t][l][r]: hidden unit unit1(i) in output row r of tile t for lane group l >> 4
+        m_t = col_of(ql.view(1, 1, 64, 1), k_.view(1, 1, 1, 4)).expand(shape)
+        p_t = par_of(k_).view(1, 1, 1, 4).expand(shape)
+        A2T = W2idx[m_t, p_t, unit1.view(1, 1, 64, 1).expand(shape)]
+        # A1T[w][g][l][r]: hidden unit 4 r + (l >> 4) for source column (4 w + (i >> 2)) E + 4 g + (i & 3)
+        cols_t = ((4 * w_.view(4, 1, 1, 1) + (il >> 2).view(1, 1, 64, 1)) * E + 4 * g_.view(1, -1, 1, 1)
+                  + (il & 3).view(1, 1, 64, 1)).expand(4, G1, 64, 4)
+        A1T = W1idx[(4 * k_.view(1, 1, 1, 4) + ql.view(1, 1, 64, 1)).expand(4, G1, 64, 4), cols_t]
+        pre = torch.full((2 * hp,), Z, dtype=torch.long)
+        index = torch.cat([A1.reshape(-1), b1m.reshape(-1), A2.reshape(-1), b2m.reshape(-1), pre,
+                           A2T.reshape(-1), A1T.reshape(-1)])
+        # the pre-scaling of the forward block (fused_wide.pack_coupling), float64
+        mul = torch.ones(index.numel(), dtype=torch.float64)
+        add = torch.zeros(index.numel(), dtype=torch.float64)
+        n_A1, n_A2, n_b2 = A1.numel(), A2.numel(), b2m.numel()
+        mul[:n_A1 + 16] = 2.0 * fused.LOG2E
+        if not shift:
+            lo = n_A1 + 16
+            logit_l = (p_l == 0).reshape(-1)
+            mul[lo:lo + n_A2][logit_l] = 0.5 * fused.LOG2E
+            lo += n_A2
+            logit_b = (p_b == 0).reshape(-1)
+            mul[lo:lo + n_b2][logit_b] = 0.5 * fused.LOG2E
+            add[lo:lo + n_b2][logit_b] = fused.AFF_C0 * fused.LOG2E
+        lo = n_A1 + 16 + n_A2 + n_b2
+        add[lo:lo + hp] = 1.0                             # pre_s = 1 (pre_t = 0)
+        self.n_fwd = lo + 2 * hp
+        self.n_bwd = int(index.numel())
+        assert self.n_bwd == int(native.lib().tfk_wide_coupling_train_bwd_param_floats(D, 1 if shift else 0))
+        self.param_index = index.to(device)
+        self.param_mul, self.param_add = mul.to(device), add.to(device)
+        self.zero = torch.zeros(1, dtype=torch.float32, device=device)
+        # the closing TFK_OP_EW_FMA block of a coupling nothing rides along with: s = 1, t = 0, no constant log-det
+        self.ew_identity = torch.cat([torch.ones(2 * hp), torch.zeros(2 * hp + 4)]).to(device)
+        self.n_ew = 4 * hp + 4
+        # one-coupling programs per lean kind (0 affine, 1 dividing affine, 2 shift forward, 3 shift inverse)
+        self.ops = {lk: ((fused.OP_AFFINE_FWD_LEAN + lk, 0, H, 0), (fused.OP_EW_FMA, 0, 0, self.n_bwd)) for lk in range(4)}
+        # (c) accumulator order of tfk_rows_outer for M >= 64: column m of A, column j of B
+        self.GH = GH = P * hp
+        u = ar(H)
+        slot = 4 * (u % 4) + u // 4                       # column of hid_rec / gpre_rec that holds unit u
+
+        def acc(m, j):                                    # (len(m), len(j)) positions of out[m][j]
+            t = 4 * (m // 64) + m % 4
+            i = (m % 64) // 4
+            return ((t * 64 + 16 * (i // 4))[:, None] + j[None, :]) * 4 + (i % 4)[:, None]
+        m2 = (ar(half)[:, None] * P + ar(P)[None, :]).reshape(-1)          # gh_rec column of (target c, parameter p)
+        dW2 = acc(m2, slot)                                                 # (TP, H)
+        db2 = acc(m2, torch.tensor([15]))[:, 0]
+        base2 = GH * 16
+        dW1 = base2 + acc(ar(half), slot).t()                               # (H, half)
+        base3 = base2 + hp * 16
+        db1 = base3 + (16 * (slot // 4) + 15) * 4 + slot % 4
+        self.acc_index = torch.cat([dW1.reshape(-1), db1, dW2.reshape(-1), db2]).to(device)
+        self.acc_sizes = (H * half, H, TP * H, TP)
+        self.acc_shapes = ((H, half), (H,), (TP, H), (TP,))
+        self.n_acc = base3 + 256
+        self.acc_out = torch.empty(self.n_acc, dtype=torch.float32, device=device)
+        self._rec = None
+        self._retired = []                                # (a captured step keeps the addresses of the buffers it saw)
+
+    def flat_of(self, lin1, lin2) -> List[torch.Tensor]:
+        return [lin1.weight.detach().reshape(-1), lin1.bias.detach(), lin2.weight.detach().reshape(-1),
+                lin2.bias.detach(), self.zero]
+
+    def pack(self, lin1, lin2) -> torch.Tensor:
+        """The ``n_bwd`` floats of (a) + (b) for the current weights (one layer; _PlanPacks packs a plan's at once)."""
+        flat = torch.cat(self.flat_of(lin1, lin2)).double()
+        return torch.addcmul(self.param_add, flat.index_select(0, self.param_index), self.param_mul).float()
+
+    def records(self, N: int):
+        """(gh_rec, gpre_rec, hid_rec) with N rows: views of buffers that only ever grow, and are never freed."""
+        if self._rec is None or self._rec[0] < N:
+            if self._rec is not None:
+                self._retired.append(self._rec)
+            cap = max(N, 2 * self._rec[0] if self._rec is not None else N)
+            mk = lambda w: torch.empty(cap, w, dtype=torch.float32, device=self.device)
+            self._rec = (cap, mk(self.GH), mk(16), mk(16))
+        _, gh, gpre, hid = self._rec
+        return gh[:N], gpre[:N], hid[:N]
+
+    def unpack_grads(self, acc: torch.Tensor):
+        """(dW1, db1, dW2, db2) from the three products' outputs."""
+        return tuple(t.view(shp) for t, shp in zip(acc.index_select(0, self.acc_index).split(self.acc_sizes),
+                                                   self.acc_shapes))
+
+
+def wide_train_enabled() -> bool:
+    """Couplings on event sizes above 256 (D % 8 == 0, D <= 1024, hidden width <= 15) train on the wide launches: one
+    tfk_flow_run_wide forward, one tfk_wide_coupling_train_bwd + three tfk_rows_outer backward
+    (TORCHFLOWS_AMD_DEBUG=wide_train=0: the layer-by-layer route; independent of ``wide``, the inference switch)."""
+    return debug_switch("wide_train", "1") != "0"
+
+
+def _fused_wide_layer(layer, D: int):
+    """(lin1, lin2) when the layer trains on the wide launches: ``_fused_bwd_layer``'s conditions above 256 columns."""
+    if not (fused_train_enabled() and wide_train_enabled()) or D <= 256:
+        return None
+    if layer.transformer.native_kind not in ("affine", "inverse_affine", "shift"):
+        return None
+    c = layer.coupling
+    if not (layer._source_is_head and layer._target_is_tail and c.source_event_size == D // 2
+            and c.target_event_size == D - D // 2):
+        return None
+    mlp = _plain_mlp(layer)
+    if mlp is None or not native.lib().tfk_wide_coupling_train_bwd_supported(D, mlp[0].out_features):
+        return None
+    if not all(p.dtype == torch.float32 for p in (mlp[0].weight, mlp[0].bias, mlp[1].weight, mlp[1].bias)):
+        return None
+    return mlp
+
+
+def _ew_fma_block(layer, d: int, D: int, hp: int):
+    """(closing TFK_OP_EW_FMA block, gscale) of a fixed ElementwiseAffine / ActNorm that rides along with a wide coupling:
+    s[2 hp] | t[2 hp] | constant log-det | pad[3] in the wide kernels' column order (each half at the head of its plane;
+    pad columns s = 1, t = 0), z = s x + t -- s = alpha, t = beta, or 1 / alpha, -beta / alpha for the dividing form,
+    evaluated in float64 as fused_wide.compile_wide does -- and the D logical column factors of its reverse mode.  Cached on
+    the layer until its value changes (ActNorm: once, at its data-dependent initialisation); the log-det constant is summed
+    on the device."""
+    key = (layer.value._version, layer.value.data_ptr(), d, hp)
+    hit = layer.__dict__.get("_tfk_ew_fma_block")
+    if hit is not None and hit[0] == key:
+        return hit[1], hit[2]
+    v = layer.value.detach().reshape(D, 2)
+    alpha = layer.transformer.constrain_scale(v[:, 0]).double()            # affine.py:33-34, the fp32 scale
+    beta = v[:, 1].double()
+    ldc = torch.log(alpha).sum().reshape(1)
+    if _affine_form_is_inverse(layer, d):
+        s, t, ldc = 1.0 / alpha, (0.0 - beta) / alpha, -ldc
+    else:
+        s, t = alpha, beta
+    half = D // 2
+    one, zero = s.new_ones(hp - half), s.new_zeros(hp - half)
+    block = torch.cat([s[:half], one, s[half:], one, t[:half], zero, t[half:], zero, ldc, s.new_zeros(3)]).float().contiguous()
+    gscale = s.float().contiguous()
+    layer.__dict__["_tfk_ew_fma_block"] = (key, block, gscale)
+    return block, gscale
+
+
 def _fused_rqs_layer(layer, D: int):
     """(lin1, lin2) when the layer can use tfk_rqs_coupling_train_bwd (and the RQS flow-program op)."""
     if not fused_train_enabled() or layer.transformer.native_kind != "rqs":
@@ -619,6 +838,36 @@ class _PlanPacks:
             self.folded_steps.update(t for t in (ew_step, rev_step) if t is not None)
             lin1, lin2 = self.rqs_layer(layer)
             self.rqs_layers.append((i, lin1, lin2, _RqsTrainPack.get(lin1.out_features, device, D)))
+        # couplings above 256 columns (the wide launches): a slot of their own, the same fold -- the fixed elementwise layer
+        # rides along in the closing TFK_OP_EW_FMA block, the reversal in the reversed store; rows are never padded
+        self.wide_layers = []                 # (plan index, lin1, lin2, _WideTrainPack, lean kind)
+        self.wide_fold = []
+        widx, wmul, wadd, off_flat = [], [], [], 0
+        for i, (layer, d, kind) in enumerate(plan):
+            mlp = _fused_wide_layer(layer, D) if (kind == "coupling" and W == D) else None
+            if mlp is None:
+                continue
+            shift = layer.transformer.native_kind == "shift"
+            pack = _WideTrainPack.get(D, mlp[0].out_features, device, shift)
+            ew_step = rev_step = None
+            j = i + 1
+            if fold and j < len(plan) and plan[j][2] == "elementwise" and not plan[j][0].value.requires_grad:
+                ew_step = j
+                j += 1
+            if fold and j < len(plan) and plan[j][2] == "perm" and plan[j][0]._is_reversal:
+                rev_step = j
+            lk = (2 + (d == INVERSE)) if shift else int(_affine_form_is_inverse(layer, d))
+            self.wide_layers.append((i, mlp[0], mlp[1], pack, lk))
+            self.wide_fold.append((ew_step, rev_step))
+            self.folded_steps.update(t for t in (ew_step, rev_step) if t is not None)
+            widx += [pack.param_index + off_flat, torch.arange(pack.n_ew, device=device) + (off_flat + pack.n_flat)]
+            wmul += [pack.param_mul, torch.ones(pack.n_ew, dtype=torch.float64, device=device)]
+            wadd += [pack.param_add, torch.zeros(pack.n_ew, dtype=torch.float64, device=device)]
+            off_flat += pack.n_flat + pack.n_ew
+        self.wide_slot = {i: k for k, (i, _, _, _, _) in enumerate(self.wide_layers)}
+        if self.wide_layers:
+            self.wide_index, self.wide_mul, self.wide_add = torch.cat(widx), torch.cat(wmul), torch.cat(wadd)
+            self.wide_sizes = [p.n_bwd + p.n_ew for _, _, _, p, _ in self.wide_layers]
         self.rqs_slot = {i: k for k, (i, _, _, _) in enumerate(self.rqs_layers)}
         self.slot = {i: k for k, (i, _, _, _) in enumerate(self.layers)}
         if not self.layers:
@@ -636,6 +885,8 @@ class _PlanPacks:
         """Every step is a permutation, a global elementwise layer or a coupling with the fused training launches:
         all gradients of the plan then come out of libtfk accumulators and can leave as slices of one buffer."""
         if not self.layers and not self.rqs_layers:
+            return False
+        if self.wide_layers:                  # (wide couplings return their gradients per tensor: no one-buffer maps yet)
             return False
         # ONE layer object (or one parameter tensor) twice in the chain (shared weights): grad_src maps a slot of the parameter buffer to exactly
         # one accumulator position, so the second use would overwrite the first instead of adding to it -- such a plan
@@ -817,11 +1068,23 @@ class _PlanPacks:
         packed = torch.cat(pieces)[self.param_index]
         return list(packed.split(self.block_sizes))
 
+    def pack_wide(self):
+        """[block of wide layer k: forward operands | A2T | A1T | closing TFK_OP_EW_FMA block] for the current weights:
+        one concatenation, one gather and one multiply-add (the lean pre-scaling, float64) for the whole plan."""
+        pieces = []
+        for (_, lin1, lin2, pack, _), (ew_step, _) in zip(self.wide_layers, self.wide_fold):
+            pieces += pack.flat_of(lin1, lin2)
+            pieces.append(pack.ew_identity if ew_step is None else
+                          _ew_fma_block(self.plan[ew_step][0], self.plan[ew_step][1], self.D, pack.hp)[0])
+        src = torch.cat(pieces).double()
+        packed = torch.addcmul(self.wide_add, src.index_select(0, self.wide_index), self.wide_mul).float()
+        return list(packed.split(self.wide_sizes))
+
 
 def _plan_packs(plan, D: int, device, fold: bool) -> _PlanPacks:
     owner = plan[0][0]
     key = (tuple(id(l) for l, _, _ in plan), tuple(d for _, d, _ in plan), str(device),
-           fused_train_enabled(), fold, padded_train_enabled(), rows_outer_enabled())
+           fused_train_enabled(), fold, padded_train_enabled(), rows_outer_enabled(), wide_train_enabled())
     cache = owner.__dict__.setdefault("_tfk_plan_packs", {})
     if key not in cache:
         if len(cache) > 4:
@@ -840,6 +1103,9 @@ def fully_fused(plan, D: int) -> bool:
     if all(_fused_bwd_layer(layer, D) is not None for layer in couplings):
         # (an event size that would need padding in a plan that cannot keep it has no fused launches after all)
         return bool(native.lib().tfk_coupling_train_bwd_supported(plan_width(plan, D)))
+    # above 256 columns: the wide forward program, tfk_wide_coupling_train_bwd and the products on tfk_rows_outer
+    if D > 256 and all(_fused_wide_layer(layer, D) is not None for layer in couplings):
+        return True
     # RQ-spline couplings: the fused launch + the row-contracting products on tfk_rows_outer (hidden width <= 15)
     def spline_ok(layer):
         mlp = _fused_rqs_layer(layer, D)
@@ -934,6 +1200,7 @@ class ChainFunction(torch.autograd.Function):
                 l2vec = packs.l2_vector(fb, maps, plan.l2)
         else:
             packed = packs.pack() if packs.layers else []
+        wide_packed = packs.pack_wide() if packs.wide_layers else []
         W = packs.W
         if W != D:                   # padded training layout: every kernel below sees (N, W) rows
             cur, cur_is_saved = packs.pad_rows(rows), False
@@ -1001,6 +1268,17 @@ class ChainFunction(torch.autograd.Function):
                 out = torch.empty_like(cur)
                 native.flow_run_mfma(cur, out, logdet, None, None, None, ops, packed[k], accumulate=started,
                                      reverse_out=rev_step is not None)
+                started = True
+                saved.append(cur)
+                cur, cur_is_saved = out, False
+            elif step in packs.wide_slot:
+                # above 256 columns: conditioner + transform (+ the fixed elementwise layer and the reversal that follow) as
+                # a one-coupling program of the wide-row chain kernel, on the head of the layer's training block
+                k = packs.wide_slot[step]
+                pack, lk = packs.wide_layers[k][3], packs.wide_layers[k][4]
+                out = torch.empty_like(cur)
+                native.flow_run_wide(cur, out, logdet, None, None, None, pack.ops[lk], wide_packed[k], accumulate=started,
+                                     reverse_out=packs.wide_fold[k][1] is not None)
                 started = True
                 saved.append(cur)
                 cur, cur_is_saved = out, False
@@ -1074,6 +1352,7 @@ class ChainFunction(torch.autograd.Function):
         ctx.saved_rows = saved
         ctx.n_params = len(params)
         ctx.packs, ctx.packed = packs, packed
+        ctx.wide_packed = wide_packed
         ctx.rqs_blocks = rqs_blocks
         ctx.kept = kept
         ctx.flat, ctx.flat_maps, ctx.l2vec = fb, maps, l2vec
@@ -1207,6 +1486,28 @@ class ChainFunction(torch.autograd.Function):
                                                      out_all[k * pack.n_out:(k + 1) * pack.n_out], pack.workspace,
                                                      inverse_form=_affine_form_is_inverse(layer, d),
                                                      gscale=gscale, g_reversed=rev_step is not None)
+                    continue
+                if i in packs.wide_slot:    # above 256 columns: one reverse-mode launch + the three row-contracting products
+                    k = packs.wide_slot[i]
+                    _, lin1, lin2, pack, _ = packs.wide_layers[k]
+                    ew_step, rev_step = packs.wide_fold[k]
+                    gscale = None
+                    if ew_step is not None:     # d(s x + t)/dx = s
+                        gscale = _ew_fma_block(plan[ew_step][0], plan[ew_step][1], D, pack.hp)[1]
+                    gh_rec, gpre_rec, hid_rec = pack.records(N)
+                    inv = (d == INVERSE) if pack.shift else _affine_form_is_inverse(layer, d)
+                    native.wide_coupling_train_bwd(x_in, g, gld, ctx.wide_packed[k][:pack.n_bwd], gh_rec, gpre_rec, hid_rec,
+                                                   shift=pack.shift, inverse_form=inv, gscale=gscale,
+                                                   g_reversed=rev_step is not None)
+                    acc, lo2, lo3 = pack.acc_out, pack.GH * 16, (pack.GH + pack.hp) * 16
+                    native.rows_outer(gh_rec, pack.GH, hid_rec, acc[:lo2])             # dW2 | db2 (column 15)
+                    native.rows_outer(x_in, pack.hp, gpre_rec, acc[lo2:lo3])           # dW1 (columns >= D / 2: not mapped)
+                    native.rows_outer(gpre_rec, 16, hid_rec, acc[lo3:])                # db1
+                    dW1, db1, dW2, db2 = pack.unpack_grads(acc)
+                    by_param = {id(lin1.weight): dW1, id(lin1.bias): db1, id(lin2.weight): dW2, id(lin2.bias): db2}
+                    grads_per_step[i] = [
+                        (by_param[id(p)] if id(p) in by_param else torch.zeros_like(p)) if p.requires_grad else None
+                        for p in cparams]
                     continue
                 if i in ctx.rqs_blocks:     # conditioner re-evaluated in the kernel, dL/dh written once
                     lin1, lin2 = packs.rqs_layer(layer)

@@ -1276,7 +1276,8 @@ int tfk_rqs_coupling_train_bwd_hid(const float *x, float *g, const float *gld, c
 // A-values of four tiles as ONE float4 (columns 64 T + 4 i + (t & 3) of tile t = 4 T + (t & 3)), so a quarter-wave reads
 // 256 contiguous bytes of a row.  Rows are strided over the waves of the grid; a workgroup adds its four waves' tiles in
 // the LDS and writes ONE partial block; k_colsum2d adds the blocks in a fixed order (deterministic).
-//   blockIdx.y = chunk of 256 columns (MT = 16 tiles) of A, or the single chunk of MT = 1 / 2 tiles (M = 16 / 32).
+//   blockIdx.y = chunk of 256 columns (MT = 16 tiles; M a multiple of 256 up to 1024) or of 64 columns (MT = 4; any other
+//   multiple of 64 up to 2048) of A, or the single chunk of MT = 1 / 2 tiles (M = 16 / 32).
 //   Output order (floats): tile t, lane (q, j), register r  ->  [(t * 64 + 16 q + j) * 4 + r] = out[col(t, 4 q + r)][j],
 //   col(t, i) = 64 (t >> 2) + 4 i + (t & 3) for MT >= 4, 16 t + i otherwise.
 // =============================================================================================
@@ -1370,8 +1371,8 @@ int tfk_rows_outer(const float *A, int32_t lda, int32_t M, const float *B, float
 {
     const char *fn = "tfk_rows_outer";
     if (N < 1) return fail(TFK_EINVAL, "%s: N = %lld < 1", fn, (long long)N);
-    if (!(M == 16 || M == 32 || (M >= 256 && M % 256 == 0)) || M > 1024)
-        return fail(TFK_EINVAL, "%s: M = %d must be 16, 32 or a multiple of 256 up to 1024", fn, M);
+    if (!(M == 16 || M == 32 || (M >= 64 && M % 64 == 0)) || M > 2048)
+        return fail(TFK_EINVAL, "%s: M = %d must be 16, 32 or a multiple of 64 up to 2048", fn, M);
     if (lda < M || (lda & 3)) return fail(TFK_EINVAL, "%s: lda = %d must be a multiple of 4 and >= M = %d", fn, lda, M);
     if (!A || !B || !out || !workspace) return fail(TFK_EINVAL, "%s: null pointer", fn);
     if (!aligned16(A) || !aligned16(B) || !aligned16(out) || !aligned16(workspace))
@@ -1385,8 +1386,10 @@ int tfk_rows_outer(const float *A, int32_t lda, int32_t M, const float *B, float
         hipLaunchKernelGGL((k_rows_outer<1>), dim3((int)grid, 1), dim3(256), 0, s, A, lda, B, workspace, (long long)N, M);
     else if (M == 32)
         hipLaunchKernelGGL((k_rows_outer<2>), dim3((int)grid, 1), dim3(256), 0, s, A, lda, B, workspace, (long long)N, M);
-    else
+    else if (M % 256 == 0 && M <= 1024)                       // (the launch shape these sizes have always had)
         hipLaunchKernelGGL((k_rows_outer<16>), dim3((int)grid, M / 256), dim3(256), 0, s, A, lda, B, workspace, (long long)N, M);
+    else                                                      // any other multiple of 64: chunks of 64 columns
+        hipLaunchKernelGGL((k_rows_outer<4>), dim3((int)grid, M / 64), dim3(256), 0, s, A, lda, B, workspace, (long long)N, M);
     if (int rc = check_launch(fn)) return rc;
     hipLaunchKernelGGL(k_colsum2d, dim3((M * 16 + 63) / 64), dim3(1024), 0, s, workspace, out, (int)grid, M * 16);
     return check_launch(fn);

@@ -8,7 +8,9 @@ applied as the pre-affine of the coupling that transforms it, flushed by the clo
 of the constant log-dets).  The rows stay at their logical width D in memory; only the parameter blocks know the padded
 plane width ``hp`` (the next multiple of 64 above D / 2).
 
-Training is out of scope here: with gradients enabled the autograd route is untouched.
+Training does not go through this packer: with gradients enabled ``autograd.ChainFunction`` runs one coupling per launch of
+the same kernel, on operands ``autograd._WideTrainPack`` gathers from the live weights (the block of ``pack_coupling`` with
+pre_s = 1, pre_t = 0), and its reverse mode on csrc/tfk_wide_bwd.h.
 """
 from __future__ import annotations
 

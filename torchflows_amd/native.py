@@ -44,6 +44,8 @@ SYMBOLS = (
     "tfk_coupling_train_bwd_workspace_bytes", "tfk_affine_coupling_train_bwd",
     "tfk_rqs_coupling_train_bwd_supported", "tfk_rqs_coupling_train_bwd", "tfk_rqs_coupling_train_bwd_hid",
     "tfk_rows_outer_workspace_bytes", "tfk_rows_outer",
+    "tfk_wide_coupling_train_bwd_supported", "tfk_wide_coupling_train_bwd_param_floats",
+    "tfk_wide_coupling_train_bwd_grid_cap", "tfk_wide_coupling_train_bwd",
     "tfk_made_affine_sequential", "tfk_made_rqs_sequential_lds_bytes", "tfk_made_rqs_sequential",
     "tfk_made_lrs_sequential_lds_bytes", "tfk_made_lrs_sequential",
     "tfk_conv3x3_block_supported", "tfk_conv3x3_relu_pool_affine", "tfk_conv1x1_frame", "tfk_bounded_sigmoid", "tfk_bounded_sigmoid_bwd",
@@ -176,6 +178,13 @@ def _bind(L: C.CDLL) -> None:
     L.tfk_rows_outer_workspace_bytes.argtypes = [_i32]
     L.tfk_rows_outer_workspace_bytes.restype = _i64
     L.tfk_rows_outer.argtypes = [_vp, _i32, _i32, _vp, _vp, _vp, _i64, _vp]
+    L.tfk_wide_coupling_train_bwd_supported.argtypes = [_i32, _i32]
+    L.tfk_wide_coupling_train_bwd_param_floats.argtypes = [_i32, _i32]
+    L.tfk_wide_coupling_train_bwd_param_floats.restype = _i64
+    L.tfk_wide_coupling_train_bwd_grid_cap.argtypes = [_i32, _i32]
+    L.tfk_wide_coupling_train_bwd_grid_cap.restype = _i64
+    L.tfk_wide_coupling_train_bwd.argtypes = [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp,
+                                              _i32, _vp]
     L.tfk_made_affine_sequential.argtypes = [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]
     L.tfk_made_rqs_sequential_lds_bytes.argtypes = [_i32, _i32, _i32]
     L.tfk_made_rqs_sequential_lds_bytes.restype = _i64
@@ -661,6 +670,32 @@ def rows_outer(A, M, B, out):
     with _device_guard(A):
         rc = lib().tfk_rows_outer(_f32(A, name), int(lda), int(M), _f32(B, name), _f32(out, name), _f32(ws, name), N,
                                   _stream(A))
+    calls += 1
+    _check(rc, name)
+
+
+def wide_coupling_train_bwd(x, g, gld, params, gh_rec, gpre_rec, hid_rec, shift=False, inverse_form=False,
+                            gscale=None, g_reversed=False):
+    """Reverse mode of one affine / shift coupling on an event size in (256, 1024], D % 8 == 0 (tfk_wide_coupling_train_bwd):
+    in place on g; gh_rec (N, 2 hp) -- (N, hp) for a shift coupling --, gpre_rec (N, 16) and hid_rec (N, 16) are the records
+    tfk_rows_outer contracts over the batch rows (include/tfk.h).  The records may be longer than N rows (buffers kept
+    across steps): only the first N are written."""
+    global calls
+    name = "tfk_wide_coupling_train_bwd"
+    N, D = _rows(g, name)
+    hp = (D // 2 + 63) // 64 * 64
+    if x.shape != g.shape or gld.numel() != N:
+        raise NativeError(f"{name}: bad x / gld shape")
+    for t, w in ((gh_rec, hp if shift else 2 * hp), (gpre_rec, 16), (hid_rec, 16)):
+        if t.dim() != 2 or t.shape[1] != w or t.shape[0] < N or not t.is_contiguous():
+            raise NativeError(f"{name}: record of shape {tuple(t.shape)}, expected (>= {N}, {w}) contiguous")
+    if gscale is not None and gscale.numel() != D:
+        raise NativeError(f"{name}: gscale must hold D = {D} floats")
+    args = (_f32(x, name), _f32(g, name), _f32(gld, name), _f32(params, name), params.numel(), _f32(gh_rec, name),
+            _f32(gpre_rec, name), _f32(hid_rec, name), N, D, 1 if shift else 0, 1 if inverse_form else 0,
+            _f32(gscale, name), 1 if g_reversed else 0)
+    with _device_guard(g):
+        rc = lib().tfk_wide_coupling_train_bwd(*args, _stream(g))
     calls += 1
     _check(rc, name)
 
