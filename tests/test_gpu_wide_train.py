@@ -1,6 +1,6 @@
-"""Training above 256 columns on the device (csrc/tfk_wide_bwd.h, torchflows_amd/autograd.py: _WideTrainPack and the wide
-slot of ChainFunction): the reverse-mode kernel through the C-ABI against float64, whole-flow gradients against fp64
-autograd and the reference's fixture, run-to-run determinism, a captured ``Flow.fit`` in a child process, and the plans
+"""Training above 256 columns on the device (csrc/tfk_wide_bwd.h, torchflows_amd/train_packs.py: _WideTrainPack,
+torchflows_amd/autograd.py: the wide route of ChainFunction): the reverse-mode kernel through the C-ABI against float64,
+whole-flow gradients against fp64 autograd and the reference's fixture, run-to-run determinism, a captured ``Flow.fit`` in a child process, and the plans
 that keep the layer-by-layer route.
 
 Sizes: the smallest at which the kernel can go wrong -- D = 264 (planes of 192, 60 pad columns each, 12 columns per lane),

@@ -1,4 +1,4 @@
-"""Host-side tests of training above 256 columns (torchflows_amd/autograd.py:_WideTrainPack, csrc/tfk_wide_bwd.h): the
+"""Host-side tests of training above 256 columns (torchflows_amd/train_packs.py:_WideTrainPack, csrc/tfk_wide_bwd.h): the
 operand block decoded exactly as the two kernels index it, the un-permute of the tfk_rows_outer outputs, the fp64 emulator
 of the whole reverse mode against torch.autograd, and which plans take the route.  No GPU needed."""
 import pytest
@@ -220,21 +220,22 @@ def test_which_plans_take_the_route(monkeypatch):
         plan = _plan(flow)
         assert ag.fully_fused(plan, D) and ag.plan_width(plan, D) == D
         packs = ag._PlanPacks(plan, D, CPU, fold=True)
-        assert len(packs.wide_layers) == 2 and not packs.layers and not packs.flat_capable()
+        wide = packs.fused[ag._WIDE]
+        assert len(wide) == 2 and wide == packs.records and not packs.fused[ag._AFFINE] and not packs.flat_capable()
         # the ActNorm behind each coupling rides along, and the reversal between the two (none follows the last one)
-        assert all(ew is not None for ew, _ in packs.wide_fold) and packs.wide_fold[0][1] is not None
+        assert all(rec.ew_step is not None for rec in wide) and wide[0].rev_step is not None
     set_debug(monkeypatch, wide_train=0)
     for flow, D in ((img, 784), (nice, 512)):
         plan = _plan(flow)
         assert not ag.fully_fused(plan, D) and ag.plan_width(plan, D) == D
-        assert not ag._PlanPacks(plan, D, CPU, fold=True).wide_layers
+        assert not ag._PlanPacks(plan, D, CPU, fold=True).fused[ag._WIDE]
     set_debug(monkeypatch, wide_train=None)
     for flow, D in ((_flow("RealNVP", 258, 2), 258),
                     (_flow("RealNVP", 784, 2, conditioner_kwargs=dict(n_hidden=16)), 784),
                     (_flow("CouplingRQNSF", 264, 1), 264)):
         plan = _plan(flow)
         assert plan is not None and not ag.fully_fused(plan, D)
-        assert not ag._PlanPacks(plan, D, CPU, fold=True).wide_layers
+        assert not ag._PlanPacks(plan, D, CPU, fold=True).fused[ag._WIDE]
     torch.manual_seed(0)
     cflow = tfa.Flow(tfa.RealNVP(512, context_shape=(3,), n_layers=2))
     plan = _plan(cflow)

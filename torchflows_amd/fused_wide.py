@@ -9,7 +9,7 @@ of the constant log-dets).  The rows stay at their logical width D in memory; on
 plane width ``hp`` (the next multiple of 64 above D / 2).
 
 Training does not go through this packer: with gradients enabled ``autograd.ChainFunction`` runs one coupling per launch of
-the same kernel, on operands ``autograd._WideTrainPack`` gathers from the live weights (the block of ``pack_coupling`` with
+the same kernel, on operands ``train_packs._WideTrainPack`` gathers from the live weights (the block of ``pack_coupling`` with
 pre_s = 1, pre_t = 0), and its reverse mode on csrc/tfk_wide_bwd.h.
 """
 from __future__ import annotations
