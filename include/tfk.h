@@ -400,6 +400,29 @@ int tfk_lrs_coupling_inv(const float *z, const float *h, float *x, float *logdet
                          const int32_t *tgt_idx, int32_t T, int32_t n_bins, float boundary,
                          int32_t accumulate, void *stream);
 
+/* ---- deep sigmoidal flow coupling (additive to ABI v29) ---------------------------------
+ * Sigmoid / DeepSigmoid (transformers/combination/sigmoid.py, combination/base.py) inside CouplingBijection.forward /
+ * inverse; csrc/tfk_dsf.hip.  Same conventions as tfk_rqs_coupling_*: rows (N, D), tgt_idx or NULL for the contiguous
+ * tail, accumulate, stream.  h is (N, T, 3 * hidden_dim * n_components): per element the components' vectors
+ * [da (K) | db (K) | dw (K)] one after the other (no alignment contract).
+ * Supported: 1 <= hidden_dim <= 16 with 1 or 2 components, 1 <= hidden_dim <= 8 with up to 4 (tfk_dsf_supported; anything
+ * else is TFK_EINVAL).
+ * inv: the bisection of bijections/numerical_inversion.py on [-10, 10] (components last to first, bracket moved on
+ * f(c) < y, result = the last midpoint) runs inside the launch, per element until the fp32 midpoint stops moving and at
+ * most 64 times; the log-det is minus the forward log-det at the returned x.
+ * bwd: reverse mode of fwd recomputed from x and h, in place on g at the target columns, gh (N, T, 3 K C) written;
+ * inverse != 0 is TFK_EINVAL (the bisection carries no gradient: that direction is differentiated on the ATen path). */
+int tfk_dsf_supported(int32_t n_components, int32_t hidden_dim);
+int tfk_dsf_coupling_fwd(const float *x, const float *h, float *z, float *logdet, int64_t N, int32_t D,
+                         const int32_t *tgt_idx, int32_t T, int32_t n_components, int32_t hidden_dim,
+                         int32_t accumulate, void *stream);
+int tfk_dsf_coupling_inv(const float *z, const float *h, float *x, float *logdet, int64_t N, int32_t D,
+                         const int32_t *tgt_idx, int32_t T, int32_t n_components, int32_t hidden_dim,
+                         int32_t accumulate, void *stream);
+int tfk_dsf_coupling_bwd(const float *x, const float *h, float *g, const float *gld, float *gh,
+                         int64_t N, int32_t D, const int32_t *tgt_idx, int32_t T, int32_t n_components,
+                         int32_t hidden_dim, int32_t inverse, void *stream);
+
 /* The SEQUENTIAL map of a MADE-based affine layer in one launch: MAF sampling
  * (MaskedAutoregressiveBijection.inverse, layers_base.py:208-221) and IAF density
  * (InverseMaskedAutoregressiveBijection.forward, :231-232), where the reference runs D conditioner

@@ -4,5 +4,6 @@ README shows (its v1.2.0 tree keeps the presets under ``bijections.finite.autore
 from torchflows_amd.bijections.finite.autoregressive.architectures import *  # noqa: F401,F403
 from torchflows_amd.bijections.finite.autoregressive.architectures import (  # noqa: F401
     RealNVP, CouplingRQNSF, CouplingLRS, NICE, MAF, IAF, MaskedAutoregressiveRQNSF,
-    InverseAutoregressiveRQNSF, MaskedAutoregressiveLRS, InverseAutoregressiveLRS)
+    InverseAutoregressiveRQNSF, MaskedAutoregressiveLRS, InverseAutoregressiveLRS, CouplingDeepSF,
+    MaskedAutoregressiveDeepSF, InverseAutoregressiveDeepSF)
 from torchflows_amd.bijections.finite.multiscale.architectures import *  # noqa: F401,F403

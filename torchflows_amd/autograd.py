@@ -73,6 +73,9 @@ def _has_reverse_mode(tr) -> bool:
     """The transformer has forward and reverse-mode kernels that read its parameters from memory (affine, RQ / LR spline)."""
     if tr.native_kind == "rqs":
         return bool(native.lib().tfk_rqs_coupling_bwd_supported(int(tr.n_bins)))
+    if tr.native_kind == "dsf":
+        from torchflows_amd.bijections.finite.autoregressive.layers_base import _dsf_native
+        return _dsf_native(tr)
     return tr.native_kind in ("affine", "inverse_affine") or (tr.native_kind == "lrs" and int(tr.n_bins) in (4, 8))
 
 
@@ -122,6 +125,9 @@ def training_plan(composition, direction: int):
             kind = _step_kind(layer)
             if kind is None or (kind == "made" and d == layer._sequential_when):
                 steps = None    # (the element-by-element map is not differentiated on the HIP path)
+                break
+            if kind == "coupling" and d == INVERSE and layer.transformer.native_kind == "dsf":
+                steps = None    # (a bisection without gradient: the ATen graph, as the reference differentiates it)
                 break
             steps.append((layer, d, kind))
     cache[direction] = (key, steps)
@@ -811,6 +817,8 @@ def _transform_forward(layer, d: int, x, h, out, logdet, tgt, T: int, accumulate
         native.rqs_coupling(x, h, out, logdet, tgt, T, tr.n_bins, tr.boundary, accumulate=accumulate, inverse=(d == INVERSE))
     elif tk == "lrs":
         native.lrs_coupling(x, h, out, logdet, tgt, T, tr.n_bins, tr.boundary, accumulate=accumulate, inverse=(d == INVERSE))
+    elif tk == "dsf":
+        native.dsf_coupling(x, h, out, logdet, tgt, T, tr.n_components, tr.hidden_dim, accumulate=accumulate, inverse=(d == INVERSE))
     elif tk == "conv1x1":
         native.conv1x1_coupling(x, h, out, logdet, tgt, T, tr.n_channels, accumulate=accumulate, inverse=(d == INVERSE))
     else:
@@ -826,6 +834,8 @@ def _transform_backward(layer, d: int, x_in, hc, g, gld, gh, tgt, T: int) -> Non
         native.rqs_coupling_bwd(x_in, hc, g, gld, gh, tgt, T, tr.n_bins, tr.boundary, inverse=(d == INVERSE))
     elif tk == "lrs":
         native.lrs_coupling_bwd(x_in, hc, g, gld, gh, tgt, T, tr.n_bins, tr.boundary, inverse=(d == INVERSE))
+    elif tk == "dsf":
+        native.dsf_coupling_bwd(x_in, hc, g, gld, gh, tgt, T, tr.n_components, tr.hidden_dim, inverse=(d == INVERSE))
     elif tk == "conv1x1":
         native.conv1x1_coupling_bwd(x_in, hc, g, gld, gh, tgt, T, tr.n_channels, inverse=(d == INVERSE))
     else:

@@ -13,6 +13,7 @@ from typing import Optional, Sequence, Type, Union
 from torchflows_amd.bijections.base import Bijection, BijectiveComposition
 from torchflows_amd.bijections.finite.autoregressive.layers import (
     ActNorm, AffineCoupling, AffineForwardMaskedAutoregressive, AffineInverseMaskedAutoregressive,
+    DeepSigmoidalCoupling, DeepSigmoidalForwardMaskedAutoregressive, DeepSigmoidalInverseMaskedAutoregressive,
     ElementwiseAffine, InverseAffineCoupling, LRSCoupling, LRSForwardMaskedAutoregressive,
     LRSInverseMaskedAutoregressive, RQSCoupling, RQSForwardMaskedAutoregressive,
     RQSInverseMaskedAutoregressive, ShiftCoupling)
@@ -106,3 +107,20 @@ class MaskedAutoregressiveLRS(AutoregressiveArchitecture):
 class InverseAutoregressiveLRS(AutoregressiveArchitecture):
     def __init__(self, event_shape: Shape, **kwargs):
         super().__init__(event_shape, base_bijection=LRSInverseMaskedAutoregressive, **kwargs)
+
+
+class CouplingDeepSF(AutoregressiveArchitecture):
+    """Huang et al. 2018 -- deep sigmoidal flow couplings (reference :226-238)."""
+
+    def __init__(self, event_shape: Shape, **kwargs):
+        super().__init__(event_shape, base_bijection=DeepSigmoidalCoupling, **kwargs)
+
+
+class InverseAutoregressiveDeepSF(AutoregressiveArchitecture):
+    def __init__(self, event_shape: Shape, **kwargs):
+        super().__init__(event_shape, base_bijection=DeepSigmoidalInverseMaskedAutoregressive, **kwargs)
+
+
+class MaskedAutoregressiveDeepSF(AutoregressiveArchitecture):
+    def __init__(self, event_shape: Shape, **kwargs):
+        super().__init__(event_shape, base_bijection=DeepSigmoidalForwardMaskedAutoregressive, **kwargs)

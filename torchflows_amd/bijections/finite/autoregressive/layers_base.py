@@ -32,6 +32,15 @@ from torchflows_amd.bijections.finite.autoregressive.transformers.base import (
 from torchflows_amd.utils import as_rows, get_batch_shape
 
 
+def _dsf_native(transformer) -> bool:
+    """A deep sigmoidal transformer of a size csrc/tfk_dsf.hip is instantiated for (tfk_dsf_supported); other sizes --
+    and all of them under TORCHFLOWS_AMD_DEBUG="dsf=0" (comparison runs) -- take the ATen composite path."""
+    from torchflows_amd.utils import debug_switch
+    if debug_switch("dsf", "1") == "0":
+        return False
+    return native.dsf_supported(transformer.n_components, transformer.hidden_dim)
+
+
 class AutoregressiveBijection(Bijection):
     """conditioner_transform -> h, transformer(x, h) (reference :14-48)."""
 
@@ -146,6 +155,8 @@ class CouplingBijection(AutoregressiveBijection):
             return 2 <= self.transformer.n_bins <= 32
         if kind == "lrs":
             return self.transformer.n_bins in (4, 8)
+        if kind == "dsf":
+            return _dsf_native(self.transformer)
         return kind in ("affine", "inverse_affine", "shift")
 
     def _native_ok(self, x, context) -> bool:
@@ -176,6 +187,10 @@ class CouplingBijection(AutoregressiveBijection):
         elif kind == "lrs":
             tr = self.transformer
             native.lrs_coupling(rows, h, out, state.logdet, tgt, T, tr.n_bins, tr.boundary,
+                                accumulate=acc, inverse=(d == INVERSE))
+        elif kind == "dsf":
+            tr = self.transformer
+            native.dsf_coupling(rows, h, out, state.logdet, tgt, T, tr.n_components, tr.hidden_dim,
                                 accumulate=acc, inverse=(d == INVERSE))
         elif kind == "shift":
             native.shift_coupling(rows, h, out, state.logdet, tgt, T, accumulate=acc,
@@ -248,6 +263,8 @@ class MaskedAutoregressiveBijection(AutoregressiveBijection):
             return 2 <= self.transformer.n_bins <= 32
         if kind == "lrs":
             return self.transformer.n_bins in (4, 8)
+        if kind == "dsf":
+            return _dsf_native(self.transformer)
         return kind in ("affine", "inverse_affine")
 
     def _native_ok(self, x, context) -> bool:
@@ -264,6 +281,9 @@ class MaskedAutoregressiveBijection(AutoregressiveBijection):
         elif kind == "rqs":
             native.rqs_coupling(rows, h, out, logdet, None, D, tr.n_bins, tr.boundary,
                                 accumulate=accumulate, inverse=transformer_inverse)
+        elif kind == "dsf":
+            native.dsf_coupling(rows, h, out, logdet, None, D, tr.n_components, tr.hidden_dim,
+                                accumulate=accumulate, inverse=transformer_inverse)
         else:
             native.lrs_coupling(rows, h, out, logdet, None, D, tr.n_bins, tr.boundary,
                                 accumulate=accumulate, inverse=transformer_inverse)
@@ -272,7 +292,8 @@ class MaskedAutoregressiveBijection(AutoregressiveBijection):
         """(W1t, b1, W2, b2) for tfk_made_affine_sequential / tfk_made_rqs_sequential -- masked,
         transposed, zero-padded to 8 / 16 / 32 / 64 hidden units -- when the layer qualifies (affine or
         8-bin RQ-spline transformer, MADE with two masked linear layers and no global parameters); cached
-        until a weight changes."""
+        until a weight changes.  None for a deep sigmoidal transformer: its sequential map is the host loop of D
+        passes below, one tfk_dsf_coupling_inv launch (bisection included) each."""
         import torch.nn as nn
         from torchflows_amd import fused
         from torchflows_amd.utils import debug_switch

@@ -28,6 +28,7 @@ SYMBOLS = (
     "tfk_shift_coupling_fwd", "tfk_shift_coupling_inv",
     "tfk_rqs_coupling_fwd", "tfk_rqs_coupling_inv",
     "tfk_lrs_coupling_fwd", "tfk_lrs_coupling_inv",
+    "tfk_dsf_supported", "tfk_dsf_coupling_fwd", "tfk_dsf_coupling_inv", "tfk_dsf_coupling_bwd",
     "tfk_conv1x1_coupling_fwd", "tfk_conv1x1_coupling_inv", "tfk_conv1x1_coupling_bwd",
     "tfk_elementwise_affine_fwd", "tfk_elementwise_affine_inv",
     "tfk_permute", "tfk_diag_gauss_logprob",
@@ -126,6 +127,11 @@ def _bind(L: C.CDLL) -> None:
     L.tfk_rqs_coupling_inv.argtypes = rqs
     L.tfk_lrs_coupling_fwd.argtypes = rqs
     L.tfk_lrs_coupling_inv.argtypes = rqs
+    L.tfk_dsf_supported.argtypes = [_i32, _i32]
+    dsf = [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _vp]
+    L.tfk_dsf_coupling_fwd.argtypes = dsf
+    L.tfk_dsf_coupling_inv.argtypes = dsf
+    L.tfk_dsf_coupling_bwd.argtypes = [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _vp]
     conv = [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp]
     L.tfk_conv1x1_coupling_fwd.argtypes = conv
     L.tfk_conv1x1_coupling_inv.argtypes = conv
@@ -389,6 +395,18 @@ def lrs_coupling(x, h, out, logdet, tgt_idx, T, n_bins, boundary, accumulate=Fal
               extra=(int(n_bins), C.c_float(float(boundary))))
 
 
+def dsf_supported(n_components, hidden_dim) -> bool:
+    """Is there a kernel for a deep sigmoidal transformer of this size (tfk_dsf_supported)?"""
+    return bool(lib().tfk_dsf_supported(int(n_components), int(hidden_dim)))
+
+
+def dsf_coupling(x, h, out, logdet, tgt_idx, T, n_components, hidden_dim, accumulate=False, inverse=False):
+    """Deep sigmoidal coupling; h: (N, T, 3 * hidden_dim * n_components).  ``inverse``: the whole bisection in the launch."""
+    _coupling("tfk_dsf_coupling_inv" if inverse else "tfk_dsf_coupling_fwd",
+              x, h, out, logdet, tgt_idx, T, 3 * int(hidden_dim) * int(n_components), accumulate,
+              extra=(int(n_components), int(hidden_dim)))
+
+
 def conv1x1_coupling(x, h, out, logdet, tgt_idx, T, n_channels, accumulate=False, inverse=False):
     """Invertible 1x1 convolution on the T target positions (n_channels x T/n_channels pixels,
     channel-major); h: (N, n + n(n-1)) LU parameters per sample."""
@@ -536,6 +554,22 @@ def lrs_coupling_bwd(x, h, g, gld, gh, tgt_idx, T, n_bins, boundary, inverse=Fal
             _idx(tgt_idx, name), T, int(n_bins), C.c_float(float(boundary)), 1 if inverse else 0)
     with _device_guard(g):
         rc = lib().tfk_lrs_coupling_bwd(*args, _stream(g))
+    calls += 1
+    _check(rc, name)
+
+
+def dsf_coupling_bwd(x, h, g, gld, gh, tgt_idx, T, n_components, hidden_dim, inverse=False):
+    """Reverse mode of ``dsf_coupling`` (forward direction only: the bisection carries no gradient)."""
+    global calls
+    name = "tfk_dsf_coupling_bwd"
+    N, D = _bwd_common(name, x, g, gld, tgt_idx, T)
+    P = 3 * int(hidden_dim) * int(n_components)
+    if h.numel() != N * T * P or gh.numel() != N * T * P:
+        raise NativeError(f"{name}: h / gh must hold N*T*P = {N * T * P} elements")
+    args = (_f32(x, name), _f32(h, name), _f32(g, name), _f32(gld, name), _f32(gh, name), N, D,
+            _idx(tgt_idx, name), T, int(n_components), int(hidden_dim), 1 if inverse else 0)
+    with _device_guard(g):
+        rc = lib().tfk_dsf_coupling_bwd(*args, _stream(g))
     calls += 1
     _check(rc, name)
 
