@@ -16,6 +16,7 @@ import pytest
 import torch
 
 from conftest import load_golden, set_debug, state_dict_of
+from dsf_reference import _within
 from test_host_dsf import FLOWS, bar, build_flow, dsf_transformer, normwise, rel
 
 pytestmark = pytest.mark.gpu
@@ -231,12 +232,6 @@ def _grads(flow, x, w):
     named = [(n, p) for n, p in flow.named_parameters() if p.requires_grad]
     grads = torch.autograd.grad((lp * w).sum(), [x] + [p for _, p in named], allow_unused=True)
     return grads[0], {n: gr for (n, _), gr in zip(named, grads[1:])}
-
-
-def _within(mine, r32, r64):
-    err = np.abs(np.asarray(mine, np.float64) - r64)
-    bound = 1e-4 * np.maximum(1.0, np.abs(r64)) + 4 * np.abs(np.asarray(r32, np.float64) - r64)
-    return int((err > bound).sum()), float(err.max()) if err.size else 0.0
 
 
 def test_flow_grads_golden_on_hip(native, monkeypatch):

@@ -4,7 +4,7 @@
 // (transformers/combination/sigmoid.py, combination/base.py) and, for the inverse, the host-driven bisection of
 // bijections/numerical_inversion.py.  h is (N, T, 3 K C): C components of [da (K) | db (K) | dw (K)] per element:
 //     a = softplus(log(e - 1 - 1e-3) + da / 1000) + 1e-3,  b = db / 1000,  w = softmax(dw / 1000)
-//     d = clip(sum_j w_j sigmoid(a_j x + b_j), 1e-6, 1 - 1e-6),  z = log d - log1p(-d)
+//     d = clip(sum_j w_j sigmoid(a_j x + b_j), 1e-6, 1 - 1e-6),  z = log d - log1p(-d)      (1 - d: dsf_logit below)
 //     log-det (as the reference has it) = K (log d - log(1 - d)) + sum_j [log w_j + log a_j + log sigmoid(c_j) + log sigmoid(-c_j)]
 //   * a workgroup takes R = BLOCK / T rows = up to BLOCK records, loads them with coalesced non-temporal reads and
 //     stores them in LDS at an odd stride, so that the per-lane reads of "my record" are bank-conflict-free
@@ -40,6 +40,21 @@ __device__ __forceinline__ float log1p_neg(float d) {
     const float u = 1.0f - d;
     const float lost = (1.0f - u) - d;
     return log_normal(u) + lost * __builtin_amdgcn_rcpf(u);
+}
+
+// z = log d - log(1 - d) with the reference's clip of d = sum_j w_j sigmoid(c_j).  Inside the clip 1 - d is taken as the
+// complement sum cd = sum_j w_j sigmoid(-c_j): fl(1 - d) knows 1 - d only to ulp(1) / (1 - d) relative (4e-5 at
+// 1 - d = 1.5e-3, 6 % beside the clip), which is the noise of z, of the root the bisection finds and of 1 / (d (1 - d)) in
+// the reverse mode there; cd keeps 1e-7 relative (d + cd = sum_j w_j = 1 to a rounding).  cd is held at or above the
+// clip's own 1 - d, so that z stays monotone across the clip's edge.  lg, lc: log d and log(1 - d).
+__device__ __forceinline__ float dsf_complement(float cd) { return fmaxf(cd, 1.0f - kDsfOneMinusEps); }
+__device__ __forceinline__ float dsf_logit(float d0, float cd, float &lg, float &lc)
+{
+    const bool inside = (d0 >= kDsfEps) && (d0 <= kDsfOneMinusEps);
+    const float d = fminf(fmaxf(d0, kDsfEps), kDsfOneMinusEps);
+    lg = log_normal(d);
+    lc = inside ? log_normal(dsf_complement(cd)) : log1p_neg(d);
+    return lg - lc;
 }
 
 // sigmoid.py: extract_parameters.  log_softmax goes through the log-sum-exp, softmax is e * (1 / sum) (ATen's CPU form).
@@ -78,37 +93,41 @@ __device__ __forceinline__ void dsf_extract(const float *p, DsfComp<K> &q)
 template <int K, bool LEAN>
 __device__ __forceinline__ float dsf_value(const DsfComp<K> &q, float x)
 {
-    float d = 0.0f;
+    float d = 0.0f, cd = 0.0f;
 #pragma unroll
     for (int j = 0; j < K; ++j) {
         const float c = q.a[j] * x + q.b[j];
         const float ac = __builtin_fabsf(c);                        // e in (0, 1]: no overflow for any c
         const float e = LEAN ? exp_lean(-ac) : exp_noovf(-ac);
         const float r = div_fast(1.0f, 1.0f + e);                   // (1 + e in [1, 2]: within half an ulp, tfk_common.h)
-        d += q.w[j] * (c >= 0.0f ? r : e * r);
+        const float er = e * r;
+        d += q.w[j] * (c >= 0.0f ? r : er);
+        cd += q.w[j] * (c >= 0.0f ? er : r);                        // sigmoid(-c)
     }
-    d = fminf(fmaxf(d, kDsfEps), kDsfOneMinusEps);
-    return log_normal(d) - log1p_neg(d);
+    float lg, lc;
+    return dsf_logit(d, cd, lg, lc);
 }
 
 // forward_1d: value and the reference's log-det
 template <int K>
 __device__ __forceinline__ float dsf_forward(const DsfComp<K> &q, float x, float &ld)
 {
-    float d = 0.0f, t3 = 0.0f;
+    float d = 0.0f, cd = 0.0f, t3 = 0.0f;
 #pragma unroll
     for (int j = 0; j < K; ++j) {
         const float c = q.a[j] * x + q.b[j];
         const float ac = __builtin_fabsf(c);
         const float e = exp_noovf(-ac);
         const float r = div_fast(1.0f, 1.0f + e);
-        d += q.w[j] * (c >= 0.0f ? r : e * r);
+        const float er = e * r;
+        d += q.w[j] * (c >= 0.0f ? r : er);
+        cd += q.w[j] * (c >= 0.0f ? er : r);
         t3 -= ac + 2.0f * log1p_pos(e);                             // log sigmoid(c) + log sigmoid(-c)
     }
-    d = fminf(fmaxf(d, kDsfEps), kDsfOneMinusEps);
-    const float lg = log_normal(d);
-    ld = (float)K * (lg - log_normal(1.0f - d)) + q.csum + t3;
-    return lg - log1p_neg(d);
+    float lg, lc;
+    const float z = dsf_logit(d, cd, lg, lc);
+    ld = (float)K * z + q.csum + t3;
+    return z;
 }
 
 // One element through all C components.  p: its record (3 K C floats, LDS).
@@ -250,6 +269,8 @@ __global__ __launch_bounds__(dsf_block(K)) void k_dsf_coupling(
 //     dL/dc_j = dL/dD0 w_j s_j (1 - s_j) + B (1 - 2 s_j);   dL/dx = sum_j dL/dc_j a_j
 //     dL/da_j = dL/dc_j x + B / a_j;  dL/db_j = dL/dc_j
 //     dL/dwp_i = w_i (dL/dD0 s_i - sum_j dL/dD0 s_j w_j) + B (1 - K w_i)       (softmax and log_softmax)
+// 1 - d, 1 - s_j and, for D0 above one half, s_j - sum_i w_i s_i are taken from t_j = sigmoid(-c_j) and cd = sum_j w_j t_j
+// (dsf_logit), which do not cancel where D0 approaches 1.
 // p holds the component's 3 K parameters on entry and their gradients on exit.
 // ---------------------------------------------------------------------------------------------
 template <int K>
@@ -257,31 +278,33 @@ __device__ __forceinline__ float dsf_bwd_comp(float *p, float x, float A, float 
 {
     DsfComp<K> q;
     dsf_extract<K>(p, q);
-    float s[K];
-    float d0 = 0.0f;
+    float s[K], t[K];                                              // sigmoid(c_j), sigmoid(-c_j)
+    float d0 = 0.0f, cd = 0.0f;
 #pragma unroll
     for (int j = 0; j < K; ++j) {
         const float c = q.a[j] * x + q.b[j];
         const float e = exp_noovf(-__builtin_fabsf(c));
         const float r = 1.0f / (1.0f + e);
-        s[j] = c >= 0.0f ? r : e * r;
+        const float er = e * r;
+        s[j] = c >= 0.0f ? r : er;
+        t[j] = c >= 0.0f ? er : r;
         d0 += q.w[j] * s[j];
+        cd += q.w[j] * t[j];
     }
     const float d = fminf(fmaxf(d0, kDsfEps), kDsfOneMinusEps);
     const bool inside = (d0 >= kDsfEps) && (d0 <= kDsfOneMinusEps);      // clamp passes the gradient on its bounds
-    const float g_d0 = inside ? (A + (float)K * B) / (d * (1.0f - d)) : 0.0f;
-    float dot = 0.0f;
-#pragma unroll
-    for (int j = 0; j < K; ++j) dot += s[j] * q.w[j];
+    const float g_d0 = inside ? (A + (float)K * B) / (d * dsf_complement(cd)) : 0.0f;      // (dsf_logit: 1 - d)
+    // s_j - sum_i s_i w_i, which cancels where one weight is close to 1: from the small side, cd - t_j above one half
+    const bool high = d0 > 0.5f;
     float gx = 0.0f;
 #pragma unroll
     for (int j = 0; j < K; ++j) {
-        const float g_c = g_d0 * q.w[j] * (s[j] * (1.0f - s[j])) + B * (1.0f - 2.0f * s[j]);
+        const float g_c = g_d0 * q.w[j] * (s[j] * t[j]) + B * (1.0f - 2.0f * s[j]);
         gx += g_c * q.a[j];
         const float g_a = g_c * x + B / q.a[j];
         const float ta = kDsfDefaultUa + div_1000(p[j]);
         const float sp = ta > 20.0f ? 1.0f : 1.0f / (1.0f + exp_noovf(-ta));     // softplus'
-        const float g_wp = q.w[j] * (g_d0 * (s[j] - dot)) + B * (1.0f - (float)K * q.w[j]);
+        const float g_wp = q.w[j] * (g_d0 * (high ? cd - t[j] : s[j] - d0)) + B * (1.0f - (float)K * q.w[j]);
         p[j] = g_a * sp / 1000.0f;
         p[K + j] = g_c / 1000.0f;
         p[2 * K + j] = g_wp / 1000.0f;
