@@ -174,7 +174,7 @@ def test_fused_golden(pkg, monkeypatch, name, arch, n_layers, variant):
 
 def test_segmented_program_matches_single_launch(pkg, monkeypatch):
     """A program split over several launches (small LDS budget) gives the same result."""
-    from torchflows_amd import fused
+    from torchflows_amd import flow_ops, fused
     monkeypatch.setenv("TORCHFLOWS_AMD_FUSED", "1")
     monkeypatch.setenv("TORCHFLOWS_AMD_MFMA", "0")     # vector-ALU programs: bitwise invariant
     torch.manual_seed(0)
@@ -182,7 +182,7 @@ def test_segmented_program_matches_single_launch(pkg, monkeypatch):
     x = torch.randn(777, 64, device="cuda")
     res = []
     for budget in (40 * 1024, 6 * 1024, 4 * 1024):
-        monkeypatch.setattr(fused, "MAX_PARAM_BYTES", budget)
+        monkeypatch.setattr(flow_ops, "MAX_PARAM_BYTES", budget)
         flow.bijection.__dict__.pop("_tfk_compiled", None)
         chain = fused.get_compiled(flow.bijection, 0, x.device)
         with torch.no_grad():
@@ -200,8 +200,8 @@ def test_segmented_program_matches_single_launch(pkg, monkeypatch):
     monkeypatch.setenv("TORCHFLOWS_AMD_MFMA", "1")
     res_m = []
     for budget in (52 * 1024, 12 * 1024):
-        monkeypatch.setattr(fused, "MAX_PARAM_BYTES_MFMA", budget)
-        monkeypatch.setattr(fused, "LEAN_BUDGET_64", budget)
+        monkeypatch.setattr(flow_ops, "MAX_PARAM_BYTES_MFMA", budget)
+        monkeypatch.setattr(flow_ops, "LEAN_BUDGET_64", budget)
         flow.bijection.__dict__.pop("_tfk_compiled", None)
         chain = fused.get_compiled(flow.bijection, 0, x.device)
         assert all(seg.mfma for seg in chain.segments)

@@ -542,11 +542,11 @@ def test_kept_optimizer_is_never_captured():
                                                        ("MaskedAutoregressiveLRS", 64, 2, 0), ("MaskedAutoregressiveRQNSF", 22, 2, 0)])
 @pytest.mark.parametrize("bf16x3", ["1", "0"])
 def test_lean_chain_packer_against_fp64_emulator(arch, D, n_layers, direction, bf16x3, monkeypatch):
-    """Host logic of the lean flow programs (fused._compile_lean: elementwise layers deferred and folded into W1 / b1,
+    """Host logic of the lean flow programs (flow_compile._compile_lean: elementwise layers deferred and folded into W1 / b1,
     pre-affines, pre-scaled logits, lane-major operands): an fp64 emulator that decodes the packed blocks exactly as
     csrc/tfk_flow_chain.h reads them must reproduce the composition's forward / inverse."""
     from lean_emulator import run_lean
-    from torchflows_amd import fused
+    from torchflows_amd import flow_compile
     import torchflows_amd as tfa
     if "@" in arch and bf16x3 == "0" and ("RQ" in arch or "LRS" in arch):
         pytest.skip("spline chains at row width 32: bf16 x 3 operands only")
@@ -576,11 +576,11 @@ def test_lean_chain_packer_against_fp64_emulator(arch, D, n_layers, direction, b
     flow.eval()
     comp = flow.bijection.double()
     order = comp.layers if direction == 0 else list(comp.layers)[::-1]
-    plan = fused._flatten(order, "forward" if direction == 0 else "inverse")
+    plan = flow_compile._flatten(order, "forward" if direction == 0 else "inverse")
     pos = torch.arange(D)
     if Dp != D:
         pos = torch.where(pos < D // 2, pos, pos - D // 2 + Dp // 2)
-    chain = fused._compile_lean(comp, plan, torch.device("cpu"), D, Dp, pos.clone(), pos.clone())
+    chain = flow_compile._compile_lean(comp, plan, torch.device("cpu"), D, Dp, pos.clone(), pos.clone())
     assert chain is not None and chain.D == Dp
     x = torch.randn(64, D, dtype=torch.float64)
     with torch.no_grad():
@@ -646,12 +646,12 @@ def test_cached_parameter_slots_follow_module_edits():
                                                 ("CouplingRQNSF", 64, 8, 0), ("CouplingRQNSF", 64, 2, 1),
                                                 ("CouplingLRS", 64, 16, 0), ("RealNVP", 22, 4, 0), ("RealNVP", 128, 6, 0)])
 def test_lean_context_programs_against_fp64_emulator(arch, D, C, direction):
-    """Conditional flows as ONE lean program (fused._compile_lean(context=True)): the context's columns of W1 as further
+    """Conditional flows as ONE lean program (flow_compile._compile_lean(context=True)): the context's columns of W1 as further
     GEMM-1 k-steps (A1c), the context-conditioned elementwise layers (TFK_OP_EWC_*, scale logits pre-scaled for exp2) and
     constant ones (TFK_OP_EW_FMA) in front of / behind the couplings -- decoded by the fp64 emulator exactly as
     csrc/tfk_flow_chain.h / tfk_flow_rqs_chain.h read them, against the composition's forward / inverse with context."""
     from lean_emulator import run_lean
-    from torchflows_amd import fused
+    from torchflows_amd import flow_compile
     import torchflows_amd as tfa
     torch.manual_seed(4)
     flow = tfa.Flow(getattr(tfa, arch)(D, context_shape=(C,), n_layers=3))
@@ -662,11 +662,11 @@ def test_lean_context_programs_against_fp64_emulator(arch, D, C, direction):
     comp = flow.bijection.double()
     Dp = D if D in (64, 128, 256) else (64 if D < 64 else 128)
     order = comp.layers if direction == 0 else list(comp.layers)[::-1]
-    plan = fused._flatten(order, "forward" if direction == 0 else "inverse")
+    plan = flow_compile._flatten(order, "forward" if direction == 0 else "inverse")
     pos = torch.arange(D)
     if Dp != D:
         pos = torch.where(pos < D // 2, pos, pos - D // 2 + Dp // 2)
-    chain = fused._compile_lean(comp, plan, torch.device("cpu"), D, Dp, pos.clone(), pos.clone(), context=True)
+    chain = flow_compile._compile_lean(comp, plan, torch.device("cpu"), D, Dp, pos.clone(), pos.clone(), context=True)
     assert chain is not None and len(chain.segments) == 1 and chain.D == Dp
     x, c = torch.randn(64, D, dtype=torch.float64), torch.randn(64, C, dtype=torch.float64)
     with torch.no_grad():

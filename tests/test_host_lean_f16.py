@@ -1,4 +1,4 @@
-"""Host logic of the split-f16 operand format of lean affine / shift couplings (fused._pack_lean(f16x2=True),
+"""Host logic of the split-f16 operand format of lean affine / shift couplings (flow_pack._pack_lean(f16x2=True),
 csrc/tfk_flow_chain.h: couple_lean_h), without a GPU: a decoder that reads the block exactly as the kernel does -- the
 W1 row order of the format, f16 pieces of weights and activations in their slot pattern, one K = 32 product per tile on
 an fp32 accumulator that starts at b2 -- composed with tests/lean_emulator.py for the closing TFK_OP_EW_FMA."""
@@ -9,7 +9,7 @@ from conftest import set_debug
 from lean_emulator import run_lean
 
 import torchflows_amd as tfa
-from torchflows_amd import fused
+from torchflows_amd import flow_compile
 
 LN2 = 0.6931471805599453
 
@@ -88,11 +88,11 @@ def _flow(arch, D, n_layers, seed=3, **kw):
 
 def _compile(comp, D, Dp, direction):
     order = comp.layers if direction == 0 else list(comp.layers)[::-1]
-    plan = fused._flatten(order, "forward" if direction == 0 else "inverse")
+    plan = flow_compile._flatten(order, "forward" if direction == 0 else "inverse")
     pos = torch.arange(D)
     if Dp != D:
         pos = torch.where(pos < D // 2, pos, pos - D // 2 + Dp // 2)
-    return fused._compile_lean(comp, plan, torch.device("cpu"), D, Dp, pos.clone(), pos.clone()), pos, plan
+    return flow_compile._compile_lean(comp, plan, torch.device("cpu"), D, Dp, pos.clone(), pos.clone()), pos, plan
 
 
 def _formats(chain):
@@ -146,16 +146,16 @@ def test_split_f16_falls_back_to_fp32_operands(case, monkeypatch):
             flow.log_prob(torch.randn(512, 64), context=torch.randn(512, 5))
         flow.eval()
         comp = flow.bijection.double()
-        plan = fused._flatten(comp.layers, "forward")
+        plan = flow_compile._flatten(comp.layers, "forward")
         pos = torch.arange(64)
-        chain = fused._compile_lean(comp, plan, dev, 64, 64, pos.clone(), pos.clone(), context=True)
+        chain = flow_compile._compile_lean(comp, plan, dev, 64, 64, pos.clone(), pos.clone(), context=True)
     elif case == "odd":
         D, w = 63, 64
         comp = _flow("RealNVP", D, 2).bijection.double()
-        plan = fused._flatten(comp.layers, "forward")
+        plan = flow_compile._flatten(comp.layers, "forward")
         l_ = torch.arange(D)
         lay = torch.where(l_ < D // 2, l_, torch.where(l_ == D // 2, torch.full_like(l_, w - 1), w // 2 + l_ - D // 2 - 1))
-        chain = fused._compile_lean(comp, plan, dev, D, w, lay, lay.clone(), context=False, odd=True)
+        chain = flow_compile._compile_lean(comp, plan, dev, D, w, lay, lay.clone(), context=False, odd=True)
     else:
         kw = dict(conditioner_kwargs=dict(n_hidden=11)) if case == "n_hidden=11" else {}
         flow = _flow("RealNVP", 64, 2, **kw)

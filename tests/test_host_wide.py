@@ -30,11 +30,11 @@ def test_wide_packer_against_fp64_emulator(arch, D, n_layers, direction):
     emulator that decodes the packed blocks exactly as csrc/tfk_flow_wide.h reads them must reproduce the composition's
     forward / inverse.  17 rows: one tile and a ragged second one."""
     from wide_emulator import run_wide
-    from torchflows_amd import fused, fused_wide
+    from torchflows_amd import flow_compile, fused, fused_wide
     flow = _flow(arch, D, n_layers)
     comp = flow.bijection.double()
     order = comp.layers if direction == 0 else list(comp.layers)[::-1]
-    plan = fused._flatten(order, "forward" if direction == 0 else "inverse")
+    plan = flow_compile._flatten(order, "forward" if direction == 0 else "inverse")
     chain = fused_wide.compile_wide(comp, plan, CPU, D, direction)
     assert chain is not None and fused_wide.is_wide(chain)
     hp = fused_wide.plane_width(D)

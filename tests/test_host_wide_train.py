@@ -42,13 +42,13 @@ def _pack_of(layer, D):
 def test_forward_block_is_the_inference_packers(arch, D):
     """(a): the head of the training block is fused_wide.pack_coupling's block for the same layer with pre_s = 1,
     pre_t = 0 -- built by one gather and one multiply-add instead of the packer's index construction."""
-    from torchflows_amd import autograd as ag, fused, fused_wide
+    from torchflows_amd import autograd as ag, flow_compile, fused, fused_wide
     layer, d, _ = _coupling(_flow(arch, D))
     pack, lin1, lin2, shift = _pack_of(layer, D)
     block = pack.pack(lin1, lin2)
     hp = fused_wide.plane_width(D)
     assert pack.hp == hp and block.numel() == pack.n_bwd and pack.n_fwd == fused_wide.block_floats(hp, not shift)
-    lk, plane, H, W1t, b1, W2p, b2p = fused._lean_coupling(layer, d, fused_wide.layout(D, CPU), D, 2 * hp)
+    lk, plane, H, W1t, b1, W2p, b2p = flow_compile._lean_coupling(layer, d, fused_wide.layout(D, CPU), D, 2 * hp)
     want = fused_wide.pack_coupling(lk, H, hp, W1t, b1, W2p, b2p, torch.ones(hp, dtype=torch.float64),
                                     torch.zeros(hp, dtype=torch.float64))
     assert plane == 0 and pack.ops[lk][0][0] == fused.OP_AFFINE_FWD_LEAN + lk

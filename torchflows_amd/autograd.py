@@ -37,7 +37,7 @@ import torch
 from torchflows_amd.utils import debug_switch
 
 from torchflows_amd import native
-from torchflows_amd.fused import _flatten
+from torchflows_amd.flow_compile import _flatten
 from torchflows_amd.train_packs import (_LAYOUTS, _RqsTrainPack, _TrainPack, _WideTrainPack,  # noqa: F401
                                         reversal_index, training_layout)
 

@@ -2,7 +2,7 @@
 
 Chains of affine / shift HalfSplit couplings (RealNVP, NICE, InverseRealNVP ...) on EVEN event sizes 256 < D <= 2048 whose
 conditioner is ``Linear(S, H) -> Tanh -> Linear(H, P)`` with H <= 16 become ONE ``tfk_flow_run_wide`` launch.  As in
-``fused._compile_lean``: reversals are folded into the column order, elementwise layers with global parameters are
+``flow_compile._compile_lean``: reversals are folded into the column order, elementwise layers with global parameters are
 deferred (a pending map x -> s x + t per physical column, folded into W1 / b1 where the column feeds a conditioner,
 applied as the pre-affine of the coupling that transforms it, flushed by the closing TFK_OP_EW_FMA together with the sum
 of the constant log-dets).  The rows stay at their logical width D in memory; only the parameter blocks know the padded
@@ -18,7 +18,9 @@ from typing import Optional
 
 import torch
 
-from torchflows_amd import fused, native
+from torchflows_amd import flow_compile, fused, native
+from torchflows_amd.flow_ops import FORWARD, LEAN_KINDS, OP_EW_FMA
+from torchflows_amd.flow_pack import _gemm1_operands, _gemm2_operands, _lanes
 from torchflows_amd.utils import debug_switch
 
 WAVES = 4                 # waves of a workgroup = column groups of a plane (csrc/tfk_flow_wide.h)
@@ -48,43 +50,24 @@ def pack_coupling(lk: int, H: int, hp: int, W1f, b1f, W2p, b2p, pre_s, pre_t) ->
     dev = W1f.device
     E = hp // 16                                               # columns per lane and plane
     P = W2p.shape[1]
-    W1pad = torch.zeros(16, hp, dtype=torch.float64, device=dev)
-    W1pad[:H] = W1f * (2.0 * fused.LOG2E)
-    b1pad = torch.zeros(16, dtype=torch.float64, device=dev)
-    b1pad[:H] = b1f * (2.0 * fused.LOG2E)
-    W2pad = torch.zeros(hp, P, 16, dtype=torch.float64, device=dev)
-    W2pad[:, :, :H] = W2p
-    b2q = b2p.clone()
-    if lk < 2:                                   # alpha = exp(u / 2 + c0) + 1e-10 = exp2((u / 2 + c0) log2 e) + 1e-10
-        W2pad[:, 0, :] *= 0.5 * fused.LOG2E
-        b2q[:, 0] = (b2q[:, 0] * 0.5 + fused.AFF_C0) * fused.LOG2E
-    lane = torch.arange(64, device=dev)
-    ql, il = lane >> 4, lane & 15
-    unit1 = 4 * (il & 3) + (il >> 2)
-    q2, r2 = il >> 2, il & 3
+    W1pad, b1pad, _ = _gemm1_operands(H, W1f, b1f)
+    W2pad, b2q = _gemm2_operands(H, W2p, b2p, affine=LEAN_KINDS[lk].family == "affine")
+    _, ql, _, unit1, q2, r2, qq, rr = _lanes(dev)
     w_ = torch.arange(WAVES, device=dev)
     k_ = torch.arange(4, device=dev)
     # A1[w][g][l][k]: hidden unit unit1(i), source column (4 w + q) E + 4 g + k
     g_ = torch.arange(E // 4, device=dev)
     cols = ((4 * w_.view(-1, 1, 1, 1) + ql.view(1, 1, 64, 1)) * E + 4 * g_.view(1, -1, 1, 1) + k_.view(1, 1, 1, 4))
     A1 = W1pad[unit1.view(1, 1, 64, 1).expand_as(cols), cols]
-    qq, rr = torch.meshgrid(torch.arange(4, device=dev), torch.arange(4, device=dev), indexing="ij")
     b1m = b1pad[4 * rr + qq]                                   # [q][r]
     # A2[w][t][l][k]: hidden unit 4 k + (l >> 4), output row i = 4 q2 + r2 of tile t of wave w
-    if P == 2:
-        T2 = E // 2
-        t_ = torch.arange(T2, device=dev)
-        m_l = (4 * w_.view(-1, 1, 1, 1) + q2.view(1, 1, 64, 1)) * E + 2 * t_.view(1, -1, 1, 1) + (r2 >> 1).view(1, 1, 64, 1)
-        p_l = (r2 & 1).view(1, 1, 64, 1)
-        m_b = (4 * w_.view(-1, 1, 1, 1) + qq.view(1, 1, 4, 4)) * E + 2 * t_.view(1, -1, 1, 1) + (rr >> 1).view(1, 1, 4, 4)
-        p_b = (rr & 1).view(1, 1, 4, 4).expand_as(m_b)
-    else:
-        T2 = E // 4
-        t_ = torch.arange(T2, device=dev)
-        m_l = (4 * w_.view(-1, 1, 1, 1) + q2.view(1, 1, 64, 1)) * E + 4 * t_.view(1, -1, 1, 1) + r2.view(1, 1, 64, 1)
-        p_l = torch.zeros_like(r2).view(1, 1, 64, 1)
-        m_b = (4 * w_.view(-1, 1, 1, 1) + qq.view(1, 1, 4, 4)) * E + 4 * t_.view(1, -1, 1, 1) + rr.view(1, 1, 4, 4)
-        p_b = torch.zeros_like(m_b)
+    # (P = 2, affine: tile t holds both parameters of 2 columns per lane group; P = 1, shift: 4 columns)
+    T2 = E * P // 4
+    t_ = torch.arange(T2, device=dev)
+    col = lambda q, r: (4 * w_.view(-1, 1, 1, 1) + q) * E + (4 // P) * t_.view(1, -1, 1, 1) + r // P
+    m_l, p_l = col(q2.view(1, 1, 64, 1), r2.view(1, 1, 64, 1)), (r2 % P).view(1, 1, 64, 1)
+    m_b = col(qq.view(1, 1, 4, 4), rr.view(1, 1, 4, 4))
+    p_b = (rr % P).view(1, 1, 4, 4).expand_as(m_b)
     shape = (WAVES, T2, 64, 4)
     A2 = W2pad[m_l.expand(shape), p_l.expand(shape), (4 * k_.view(1, 1, 1, 4) + ql.view(1, 1, 64, 1)).expand(shape)]
     b2m = b2q[m_b, p_b]                                        # [w][t][q][r]
@@ -98,7 +81,7 @@ def block_floats(hp: int, affine: bool) -> int:
 
 
 def compile_wide(composition, plan, device, D: int, direction: int) -> Optional["fused.CompiledChain"]:
-    """``plan`` (``fused._flatten`` of the composition in ``direction``) as one wide segment, or None."""
+    """``plan`` (``flow_compile._flatten`` of the composition in ``direction``) as one wide segment, or None."""
     from torchflows_amd.bijections.finite.autoregressive.layers_base import CouplingBijection, ElementwiseBijection
     from torchflows_amd.bijections.finite.matrix.permutation import PermutationMatrix
     if plan is None or D % 2 or D <= 256 or not native.lib().tfk_flow_wide_supported(D, 1):
@@ -107,34 +90,25 @@ def compile_wide(composition, plan, device, D: int, direction: int) -> Optional[
     Dp = 2 * hp
     pos_in = layout(D, device)
     pos = pos_in.clone()
-    s = torch.ones(Dp, dtype=torch.float64, device=device)
-    t = torch.zeros(Dp, dtype=torch.float64, device=device)
-    ld_const = torch.zeros((), dtype=torch.float64, device=device)
+    pending = flow_compile._PendingMap(Dp, device)
     ops, blocks, used, kind0 = [], [], 0, None
     with torch.no_grad():
         for layer, d in plan:
             if isinstance(layer, PermutationMatrix):
-                perm = (layer._fwd_index if d == fused.FORWARD else layer._inv_index).to(device)
+                perm = (layer._fwd_index if d == FORWARD else layer._inv_index).to(device)
                 pos = pos[perm]
             elif isinstance(layer, ElementwiseBijection):
-                got = fused._lean_elementwise(layer, d, D)
+                got = flow_compile._lean_elementwise(layer, d, D)
                 if got is None:
                     return None
-                alpha, beta, divide = got
-                if divide:
-                    s[pos] = s[pos] / alpha
-                    t[pos] = (t[pos] - beta) / alpha
-                    ld_const = ld_const - torch.log(alpha).sum()
-                else:
-                    s[pos] = alpha * s[pos]
-                    t[pos] = alpha * t[pos] + beta
-                    ld_const = ld_const + torch.log(alpha).sum()
+                pending.compose(pos, *got)
             elif isinstance(layer, CouplingBijection):
-                got = fused._lean_coupling(layer, d, pos, D, Dp)
+                got = flow_compile._lean_coupling(layer, d, pos, D, Dp)
                 if got is None:
                     return None
                 lk, plane, H, W1t, b1, W2p, b2p = got
-                if lk > 3 or not native.lib().tfk_flow_wide_supported(D, H) or len(ops) == MAX_COUPLINGS:
+                if (LEAN_KINDS[lk].family not in ("affine", "shift") or not native.lib().tfk_flow_wide_supported(D, H)
+                        or len(ops) == MAX_COUPLINGS):
                     return None
                 if kind0 is None:
                     kind0 = lk
@@ -142,20 +116,17 @@ def compile_wide(composition, plan, device, D: int, direction: int) -> Optional[
                     return None                               # (a program holds couplings of one kind)
                 src = torch.arange(plane * hp, (plane + 1) * hp, device=device)
                 tgt = torch.arange((1 - plane) * hp, (2 - plane) * hp, device=device)
-                b1f = b1 + W1t @ t[src]                       # W1 (s x + t) + b1 = (W1 s) x + (W1 t + b1)
-                W1f = W1t * s[src]
-                block = pack_coupling(lk, H, hp, W1f, b1f, W2p, b2p, s[tgt].clone(), t[tgt].clone())
-                ops.append((fused.OP_AFFINE_FWD_LEAN + lk, plane, H, used))
+                W1f, b1f = pending.fold(W1t, b1, src)
+                block = pack_coupling(lk, H, hp, W1f, b1f, W2p, b2p, *pending.take(tgt))
+                ops.append((LEAN_KINDS[lk].op, plane, H, used))
                 blocks.append(block)
                 used += block.numel()
-                s[tgt] = 1.0
-                t[tgt] = 0.0
             else:
                 return None
     if not ops:
         return None
-    ops.append((fused.OP_EW_FMA, 0, 0, used))
-    blocks.append(torch.cat([s, t, ld_const.reshape(1), ld_const.new_zeros(3)]).float())
+    ops.append((OP_EW_FMA, 0, 0, used))
+    blocks.append(pending.flush())
     seg = fused.Segment(ops, torch.cat(blocks).contiguous(), True, wide=True)
     return fused.CompiledChain(Dp, [seg], pos, bool(torch.equal(pos, pos_in)), fused._params_version(composition),
                                D_log=D, pos_in=pos_in)

@@ -1156,7 +1156,7 @@ def flow_sum_workspace(t: torch.Tensor) -> torch.Tensor:
 def flow_run_mfma(x, z, logdet, gauss_loc, gauss_log_scale, logprob, ops, params, accumulate=False,
                   reverse_out=False, base_of_input=False, D=None, context=None, sum_out=None):
     """Fused flow program with the conditioner GEMMs on the matrix cores (tfk_flow_run_mfma).
-    ops: list of (kind, src_plane, gemm2_steps, offset); params packed by fused._pack_mfma.
+    ops: list of (kind, src_plane, gemm2_steps, offset); params packed by flow_pack._pack_mfma.
     ``D``: the kernel's row width when ``x`` is narrower (lean programs, tfk_flow_run_mfma_in): x (N, x_width) is read
     half by half into the heads of the two planes."""
     global calls

@@ -248,7 +248,7 @@ class _WideTrainPack:
         return cls._cache[key]
 
     def __init__(self, D: int, H: int, device, shift: bool = False):
-        from torchflows_amd import fused
+        from torchflows_amd import flow_ops
         half = D // 2
         hp = (half + 63) // 64 * 64
         E = hp // 16
@@ -312,15 +312,15 @@ class _WideTrainPack:
         mul = torch.ones(index.numel(), dtype=torch.float64)
         add = torch.zeros(index.numel(), dtype=torch.float64)
         n_A1, n_A2, n_b2 = A1.numel(), A2.numel(), b2m.numel()
-        mul[:n_A1 + 16] = 2.0 * fused.LOG2E
+        mul[:n_A1 + 16] = 2.0 * flow_ops.LOG2E
         if not shift:
             lo = n_A1 + 16
             logit_l = (p_l == 0).reshape(-1)
-            mul[lo:lo + n_A2][logit_l] = 0.5 * fused.LOG2E
+            mul[lo:lo + n_A2][logit_l] = 0.5 * flow_ops.LOG2E
             lo += n_A2
             logit_b = (p_b == 0).reshape(-1)
-            mul[lo:lo + n_b2][logit_b] = 0.5 * fused.LOG2E
-            add[lo:lo + n_b2][logit_b] = fused.AFF_C0 * fused.LOG2E
+            mul[lo:lo + n_b2][logit_b] = 0.5 * flow_ops.LOG2E
+            add[lo:lo + n_b2][logit_b] = flow_ops.AFF_C0 * flow_ops.LOG2E
         lo = n_A1 + 16 + n_A2 + n_b2
         add[lo:lo + hp] = 1.0                             # pre_s = 1 (pre_t = 0)
         self.n_fwd = lo + 2 * hp
@@ -333,7 +333,7 @@ class _WideTrainPack:
         self.ew_identity = torch.cat([torch.ones(2 * hp), torch.zeros(2 * hp + 4)]).to(device)
         self.n_ew = 4 * hp + 4
         # one-coupling programs per lean kind (0 affine, 1 dividing affine, 2 shift forward, 3 shift inverse)
-        self.ops = {lk: ((fused.OP_AFFINE_FWD_LEAN + lk, 0, H, 0), (fused.OP_EW_FMA, 0, 0, self.n_bwd)) for lk in range(4)}
+        self.ops = {lk: ((flow_ops.LEAN_KINDS[lk].op, 0, H, 0), (flow_ops.OP_EW_FMA, 0, 0, self.n_bwd)) for lk in range(4)}
         # (c) accumulator order of tfk_rows_outer for M >= 64: column m of A, column j of B
         self.GH = GH = P * hp
         u = ar(H)
