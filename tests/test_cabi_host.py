@@ -1,7 +1,7 @@
 """The C-ABI of include/tfk.h as exported by the CPU restatement (oracle/oracle_tfk.c, host pointers, stream = NULL;
 SURVEY.md 8(b)): the same ctypes call sequence a reference-side binding would make against libtfk.so, here run on the
 host against the REFERENCE's golden outputs -- and that libtfk.so itself exports every symbol the header declares
-(no compute calls without a GPU)."""
+(no compute calls without a GPU), bound by a table (``native.bind``) that agrees with every prototype of the header."""
 import ctypes as C
 import os
 import re
@@ -12,7 +12,7 @@ import pytest
 from conftest import load_golden
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_vp, _i64, _i32, _f = C.c_void_p, C.c_int64, C.c_int32, C.c_float
+_vp, _f = C.c_void_p, C.c_float
 
 
 def rel(a, b):
@@ -25,18 +25,72 @@ def ptr(a):
 
 @pytest.fixture(scope="module")
 def cpu_abi(oracle):
+    """The CPU restatement, bound from the same table as libtfk.so (the symbols it exports)."""
+    from torchflows_amd import native
     L = C.CDLL(oracle.build())
-    L.tfk_last_error.restype = C.c_char_p
-    coupling = [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _vp]
-    for d in ("fwd", "inv"):
-        getattr(L, f"tfk_affine_coupling_{d}").argtypes = coupling
-        getattr(L, f"tfk_shift_coupling_{d}").argtypes = coupling
-        getattr(L, f"tfk_rqs_coupling_{d}").argtypes = [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _f, _i32, _vp]
-        getattr(L, f"tfk_elementwise_affine_{d}").argtypes = [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]
-    L.tfk_permute.argtypes = [_vp, _vp, _vp, _i64, _i32, _vp]
-    L.tfk_diag_gauss_logprob.argtypes = [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp]
-    L.tfk_sum_f32.argtypes = [_vp, _vp, _i64, _vp]
+    native.bind(L, [s for s in native.SYMBOLS if hasattr(L, s)])
     return L
+
+
+# ---- the binding table against the header's text -------------------------------------------------------------------
+_STRUCTURES = {"tfk_glow_layer": "GlowLayer", "tfk_glow_level_step": "GlowLevelStep",
+               "tfk_convnet_train_plan": "ConvNetTrainPlan"}
+
+
+def _ctype_class(t, native):
+    """The class of tests/tfk_header.py a ctypes type stands for."""
+    if t is None:
+        return None
+    if t in (C.c_void_p, C.c_char_p):
+        return "ptr"
+    if isinstance(t, type) and issubclass(t, C._Pointer):
+        for cname, pyname in _STRUCTURES.items():
+            if t._type_ is getattr(native, pyname):
+                return "ptr:" + cname
+        return "ptr"
+    if isinstance(t, type) and issubclass(t, C.Structure):
+        for cname, pyname in _STRUCTURES.items():
+            if t is getattr(native, pyname):
+                return "struct:" + cname
+    return {C.c_int32: "i32", C.c_int64: "i64", C.c_float: "f32"}[t]
+
+
+def _same_class(bound: str, declared: str) -> bool:
+    # a pointer to one of the header's structs is bound as POINTER(<its structure>), or as void * where the caller passes byref
+    return bound == declared or (declared.startswith("ptr:") and bound == "ptr")
+
+
+def test_binding_table_matches_every_prototype():
+    """Every function include/tfk.h declares has a row in native's table with the same number of parameters, the same
+    class (struct pointer / pointer / int32 / int64 / float) at every position and the same return class -- what the
+    name-only checks cannot see: an argument dropped from a 23-parameter list shifts every later one."""
+    import tfk_header
+    from torchflows_amd import native
+    protos = tfk_header.prototypes()
+    assert len(protos) == 89 and list(protos) == list(native.SYMBOLS)          # the table follows the header's order
+    for name, (ret, params) in protos.items():
+        restype, argtypes = native._ABI[name]
+        bound = [_ctype_class(t, native) for t in argtypes]
+        assert len(bound) == len(params), f"{name}: {len(bound)} argtypes for {len(params)} parameters"
+        for k, (b, (cls, pname)) in enumerate(zip(bound, params)):
+            assert _same_class(b, cls), f"{name}: argument {k} ({pname}) is {cls} in the header, bound as {b}"
+        assert _ctype_class(restype, native) == ret, f"{name}: returns {ret} in the header, restype says {restype}"
+
+
+def test_structures_match_the_header():
+    """The three ctypes structures: as many fields as their typedef struct, the same classes, the same order."""
+    import tfk_header
+    from torchflows_amd import native
+    declared = tfk_header.structs()
+    assert sorted(declared) == sorted(_STRUCTURES)
+    for cname, pyname in _STRUCTURES.items():
+        fields = getattr(native, pyname)._fields_
+        assert [n for n, _ in fields] == [n for _, n, _ in declared[cname]], cname
+        for (fname, ftype), (cls, _, count) in zip(fields, declared[cname]):
+            if count is not None:
+                assert issubclass(ftype, C.Array) and ftype._length_ == count, f"{cname}.{fname}"
+                ftype = ftype._type_
+            assert _ctype_class(ftype, native) == cls, f"{cname}.{fname}: {cls} in the header"
 
 
 def declared_symbols():

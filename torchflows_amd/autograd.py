@@ -69,16 +69,6 @@ def live_forced() -> bool:
     return getattr(_live, "on", False)
 
 
-def _has_reverse_mode(tr) -> bool:
-    """The transformer has forward and reverse-mode kernels that read its parameters from memory (affine, RQ / LR spline)."""
-    if tr.native_kind == "rqs":
-        return bool(native.lib().tfk_rqs_coupling_bwd_supported(int(tr.n_bins)))
-    if tr.native_kind == "dsf":
-        from torchflows_amd.bijections.finite.autoregressive.layers_base import _dsf_native
-        return _dsf_native(tr)
-    return tr.native_kind in ("affine", "inverse_affine") or (tr.native_kind == "lrs" and int(tr.n_bins) in (4, 8))
-
-
 def _step_kind(layer) -> Optional[str]:
     from torchflows_amd.bijections.finite.autoregressive.layers_base import (
         CouplingBijection, ElementwiseBijection, MaskedAutoregressiveBijection)
@@ -88,7 +78,9 @@ def _step_kind(layer) -> Optional[str]:
     if isinstance(layer, MaskedAutoregressiveBijection):
         # the parallel pass (MAF density / IAF sampling): MADE on PyTorch-ROCm, the transformer's
         # forward and reverse-mode kernels with every position a target
-        return "made" if (layer.context_shape is None and _has_reverse_mode(layer.transformer)) else None
+        tr = layer.transformer
+        ok = layer.context_shape is None and native.made_kernel(tr) and native.reverse_kernel(tr)
+        return "made" if ok else None
     if isinstance(layer, ElementwiseBijection):
         if layer.transformer.native_kind not in ("affine", "inverse_affine"):
             return None
@@ -97,11 +89,8 @@ def _step_kind(layer) -> Optional[str]:
         return "elementwise" if layer.use_global_parameters else "elementwise_ctx"
     if isinstance(layer, CouplingBijection):
         # (a context only enters the conditioner, by concatenation: conditioning/context.py:38-64)
-        kind = layer.transformer.native_kind
-        if kind == "shift" or _has_reverse_mode(layer.transformer):
+        if native.reverse_kernel(layer.transformer):
             return "coupling"
-        if kind == "conv1x1" and int(layer.transformer.n_channels) <= 16:
-            return "coupling"           # Glow's invertible 1x1 convolution (linear/convolution.py:33-64)
     return None
 
 
@@ -810,36 +799,12 @@ def _awaits_statistics(layer, d: int) -> bool:
 def _transform_forward(layer, d: int, x, h, out, logdet, tgt, T: int, accumulate: bool) -> None:
     """The transformer's forward kernel on the T target columns ``tgt`` (None: the tail) with the parameters ``h``.  ``d``: the
     step's direction -- FORWARD for a pass that always applies ``transformer.forward`` (MADE's: layers_base.py:196-199)."""
-    tk, tr = layer.transformer.native_kind, layer.transformer
-    if tk in ("affine", "inverse_affine"):
-        native.affine_coupling(x, h, out, logdet, tgt, T, accumulate=accumulate, inverse=_affine_form_is_inverse(layer, d))
-    elif tk == "rqs":
-        native.rqs_coupling(x, h, out, logdet, tgt, T, tr.n_bins, tr.boundary, accumulate=accumulate, inverse=(d == INVERSE))
-    elif tk == "lrs":
-        native.lrs_coupling(x, h, out, logdet, tgt, T, tr.n_bins, tr.boundary, accumulate=accumulate, inverse=(d == INVERSE))
-    elif tk == "dsf":
-        native.dsf_coupling(x, h, out, logdet, tgt, T, tr.n_components, tr.hidden_dim, accumulate=accumulate, inverse=(d == INVERSE))
-    elif tk == "conv1x1":
-        native.conv1x1_coupling(x, h, out, logdet, tgt, T, tr.n_channels, accumulate=accumulate, inverse=(d == INVERSE))
-    else:
-        native.shift_coupling(x, h, out, logdet, tgt, T, accumulate=accumulate, inverse=(d == INVERSE))
+    native.transform(layer.transformer, d == INVERSE, x, h, out, logdet, tgt, T, accumulate)
 
 
 def _transform_backward(layer, d: int, x_in, hc, g, gld, gh, tgt, T: int) -> None:
     """Reverse mode of ``_transform_forward``: in place on ``g`` at the target columns, dL/dh written to ``gh``."""
-    tk, tr = layer.transformer.native_kind, layer.transformer
-    if tk in ("affine", "inverse_affine"):
-        native.affine_coupling_bwd(x_in, hc, g, gld, gh, tgt, T, inverse=_affine_form_is_inverse(layer, d))
-    elif tk == "rqs":
-        native.rqs_coupling_bwd(x_in, hc, g, gld, gh, tgt, T, tr.n_bins, tr.boundary, inverse=(d == INVERSE))
-    elif tk == "lrs":
-        native.lrs_coupling_bwd(x_in, hc, g, gld, gh, tgt, T, tr.n_bins, tr.boundary, inverse=(d == INVERSE))
-    elif tk == "dsf":
-        native.dsf_coupling_bwd(x_in, hc, g, gld, gh, tgt, T, tr.n_components, tr.hidden_dim, inverse=(d == INVERSE))
-    elif tk == "conv1x1":
-        native.conv1x1_coupling_bwd(x_in, hc, g, gld, gh, tgt, T, tr.n_channels, inverse=(d == INVERSE))
-    else:
-        native.shift_coupling_bwd(g, gh, tgt, T, inverse=(d == INVERSE))
+    native.transform_bwd(layer.transformer, d == INVERSE, x_in, hc, g, gld, gh, tgt, T)
 
 
 def _mlp_param_grads(cparams, lin1, lin2, dW1, db1, dW2, db2) -> List[Optional[torch.Tensor]]:

@@ -32,15 +32,6 @@ from torchflows_amd.bijections.finite.autoregressive.transformers.base import (
 from torchflows_amd.utils import as_rows, get_batch_shape
 
 
-def _dsf_native(transformer) -> bool:
-    """A deep sigmoidal transformer of a size csrc/tfk_dsf.hip is instantiated for (tfk_dsf_supported); other sizes --
-    and all of them under TORCHFLOWS_AMD_DEBUG="dsf=0" (comparison runs) -- take the ATen composite path."""
-    from torchflows_amd.utils import debug_switch
-    if debug_switch("dsf", "1") == "0":
-        return False
-    return native.dsf_supported(transformer.n_components, transformer.hidden_dim)
-
-
 class AutoregressiveBijection(Bijection):
     """conditioner_transform -> h, transformer(x, h) (reference :14-48)."""
 
@@ -148,16 +139,7 @@ class CouplingBijection(AutoregressiveBijection):
     # -- HIP path ------------------------------------------------------------------
     def _native_supported(self) -> bool:
         """Is there a libtfk kernel for this layer's transformer?"""
-        kind = self.transformer.native_kind
-        if kind == "conv1x1":
-            return self.transformer.n_channels <= 16     # channels are kept in registers
-        if kind == "rqs":
-            return 2 <= self.transformer.n_bins <= 32
-        if kind == "lrs":
-            return self.transformer.n_bins in (4, 8)
-        if kind == "dsf":
-            return _dsf_native(self.transformer)
-        return kind in ("affine", "inverse_affine", "shift")
+        return native.coupling_kernel(self.transformer)
 
     def _native_ok(self, x, context) -> bool:
         return self._native_supported() and native.eligible(x, context) and _params_ok(self)
@@ -175,31 +157,7 @@ class CouplingBijection(AutoregressiveBijection):
         h = self.conditioner_transform(x_a, context=ctx).reshape(N, -1).contiguous()
         out = rows if state.owned else state.out_buffer()
         tgt = None if self._target_is_tail else self._target_index32
-        acc = state.started
-        kind = self.transformer.native_kind
-        if kind in ("affine", "inverse_affine"):
-            inv = (d == INVERSE) != (kind == "inverse_affine")
-            native.affine_coupling(rows, h, out, state.logdet, tgt, T, accumulate=acc, inverse=inv)
-        elif kind == "rqs":
-            tr = self.transformer
-            native.rqs_coupling(rows, h, out, state.logdet, tgt, T, tr.n_bins, tr.boundary,
-                                accumulate=acc, inverse=(d == INVERSE))
-        elif kind == "lrs":
-            tr = self.transformer
-            native.lrs_coupling(rows, h, out, state.logdet, tgt, T, tr.n_bins, tr.boundary,
-                                accumulate=acc, inverse=(d == INVERSE))
-        elif kind == "dsf":
-            tr = self.transformer
-            native.dsf_coupling(rows, h, out, state.logdet, tgt, T, tr.n_components, tr.hidden_dim,
-                                accumulate=acc, inverse=(d == INVERSE))
-        elif kind == "shift":
-            native.shift_coupling(rows, h, out, state.logdet, tgt, T, accumulate=acc,
-                                  inverse=(d == INVERSE))
-        elif kind == "conv1x1":
-            native.conv1x1_coupling(rows, h, out, state.logdet, tgt, T, self.transformer.n_channels,
-                                    accumulate=acc, inverse=(d == INVERSE))
-        else:
-            raise native.NativeError(f"no kernel for transformer kind {kind!r}")
+        native.transform(self.transformer, d == INVERSE, rows, h, out, state.logdet, tgt, T, state.started)
         state.started = True
         state.commit(out)
 
@@ -258,14 +216,7 @@ class MaskedAutoregressiveBijection(AutoregressiveBijection):
 
     # -- HIP path ----------------------------------------------------------------------
     def _native_supported(self) -> bool:
-        kind = self.transformer.native_kind
-        if kind == "rqs":
-            return 2 <= self.transformer.n_bins <= 32
-        if kind == "lrs":
-            return self.transformer.n_bins in (4, 8)
-        if kind == "dsf":
-            return _dsf_native(self.transformer)
-        return kind in ("affine", "inverse_affine")
+        return native.made_kernel(self.transformer)
 
     def _native_ok(self, x, context) -> bool:
         return self._native_supported() and native.eligible(x, context) and _params_ok(self)
@@ -274,19 +225,7 @@ class MaskedAutoregressiveBijection(AutoregressiveBijection):
         N, D = rows.shape
         ctx = None if context is None else context.reshape(N, *self.context_shape)
         h = self.conditioner_transform(rows.view(N, *self.event_shape), ctx).reshape(N, -1).contiguous()
-        kind, tr = self.transformer.native_kind, self.transformer
-        if kind in ("affine", "inverse_affine"):
-            native.affine_coupling(rows, h, out, logdet, None, D, accumulate=accumulate,
-                                   inverse=transformer_inverse != (kind == "inverse_affine"))
-        elif kind == "rqs":
-            native.rqs_coupling(rows, h, out, logdet, None, D, tr.n_bins, tr.boundary,
-                                accumulate=accumulate, inverse=transformer_inverse)
-        elif kind == "dsf":
-            native.dsf_coupling(rows, h, out, logdet, None, D, tr.n_components, tr.hidden_dim,
-                                accumulate=accumulate, inverse=transformer_inverse)
-        else:
-            native.lrs_coupling(rows, h, out, logdet, None, D, tr.n_bins, tr.boundary,
-                                accumulate=accumulate, inverse=transformer_inverse)
+        native.transform(self.transformer, transformer_inverse, rows, h, out, logdet, None, D, accumulate)
 
     def _made_pack(self):
         """(W1t, b1, W2, b2) for tfk_made_affine_sequential / tfk_made_rqs_sequential -- masked,

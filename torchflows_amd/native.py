@@ -12,7 +12,8 @@ import ctypes as C
 import os
 import struct
 import subprocess
-from typing import Optional
+from operator import attrgetter
+from typing import Callable, NamedTuple, Optional
 
 import torch
 
@@ -20,45 +21,6 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 # TORCHFLOWS_AMD_LIB: load another build of the same ABI (kernel experiments / ablations)
 LIB_PATH = os.environ.get("TORCHFLOWS_AMD_LIB") or os.path.join(_PKG, "lib", "libtfk.so")
 CSRC = os.path.join(_PKG, "csrc")
-
-# every symbol include/tfk.h declares (tests check the built library exports all of them)
-SYMBOLS = (
-    "tfk_abi_version", "tfk_last_error", "tfk_device_info",
-    "tfk_affine_coupling_fwd", "tfk_affine_coupling_inv",
-    "tfk_shift_coupling_fwd", "tfk_shift_coupling_inv",
-    "tfk_rqs_coupling_fwd", "tfk_rqs_coupling_inv",
-    "tfk_lrs_coupling_fwd", "tfk_lrs_coupling_inv",
-    "tfk_dsf_supported", "tfk_dsf_coupling_fwd", "tfk_dsf_coupling_inv", "tfk_dsf_coupling_bwd",
-    "tfk_conv1x1_coupling_fwd", "tfk_conv1x1_coupling_inv", "tfk_conv1x1_coupling_bwd",
-    "tfk_elementwise_affine_fwd", "tfk_elementwise_affine_inv",
-    "tfk_permute", "tfk_diag_gauss_logprob",
-    "tfk_sum_workspace_bytes", "tfk_sum_f32", "tfk_sum_f32_ws",
-    "tfk_flow_supported", "tfk_flow_run",
-    "tfk_flow_mfma_supported", "tfk_flow_lean_supported", "tfk_flow_run_mfma", "tfk_flow_run_mfma_in", "tfk_flow_run_mfma_ctx",
-    "tfk_flow_sum_workspace_bytes", "tfk_flow_run_mfma_sum",
-    "tfk_flow_wide_supported", "tfk_flow_run_wide",
-    "tfk_affine_coupling_bwd", "tfk_shift_coupling_bwd",
-    "tfk_rqs_coupling_bwd_supported", "tfk_rqs_coupling_bwd", "tfk_lrs_coupling_bwd",
-    "tfk_elementwise_affine_bwd_workspace_bytes", "tfk_elementwise_affine_bwd",
-    "tfk_diag_gauss_logprob_bwd",
-    "tfk_coupling_train_bwd_supported", "tfk_coupling_train_bwd_out_floats",
-    "tfk_coupling_train_bwd_workspace_bytes", "tfk_affine_coupling_train_bwd",
-    "tfk_rqs_coupling_train_bwd_supported", "tfk_rqs_coupling_train_bwd", "tfk_rqs_coupling_train_bwd_hid",
-    "tfk_rows_outer_workspace_bytes", "tfk_rows_outer",
-    "tfk_wide_coupling_train_bwd_supported", "tfk_wide_coupling_train_bwd_param_floats",
-    "tfk_wide_coupling_train_bwd_grid_cap", "tfk_wide_coupling_train_bwd",
-    "tfk_made_affine_sequential", "tfk_made_rqs_sequential_lds_bytes", "tfk_made_rqs_sequential",
-    "tfk_made_lrs_sequential_lds_bytes", "tfk_made_lrs_sequential",
-    "tfk_conv3x3_block_supported", "tfk_conv3x3_relu_pool_affine", "tfk_conv1x1_frame", "tfk_bounded_sigmoid", "tfk_bounded_sigmoid_bwd",
-    "tfk_glow_weight_floats", "tfk_glow_plan", "tfk_glow_coupling", "tfk_rows_fma",
-    "tfk_glow_level_blob_bytes", "tfk_glow_level_pack", "tfk_glow_level_info", "tfk_glow_level",
-    "tfk_rows_fma_gauss_logprob",
-    "tfk_convnet_train_workspace_bytes", "tfk_convnet_train_block_supported", "tfk_convnet_train_block_fwd",
-    "tfk_convnet_train_block_bwd", "tfk_convnet_train_frame_fwd", "tfk_convnet_train_frame_bwd",
-    "tfk_convnet_train_linear_wgrad", "tfk_convnet_train_linear_fwd", "tfk_convnet_train_linear_bwd_input",
-    "tfk_convnet_train_linear_prep", "tfk_convnet_train_forward", "tfk_convnet_train_backward",
-    "tfk_convnet_train_sums_floats",
-)
 
 ABI_VERSION = 29
 
@@ -70,7 +32,6 @@ class NativeError(RuntimeError):
 _vp = C.c_void_p
 _i32 = C.c_int32
 _i64 = C.c_int64
-
 
 
 class GlowLayer(C.Structure):
@@ -104,6 +65,115 @@ class GlowLevelStep(C.Structure):
                 ("w4", _vp), ("b4", _vp), ("weights_host", _vp)]
 
 
+# The C-ABI, once: name -> (restype, argtypes) for every function include/tfk.h declares, in the header's order
+# (tests/test_cabi_host.py holds each row to its prototype, parameter by parameter).  A signature the header repeats is
+# one list here.
+_int, _f, _pi = C.c_int, C.c_float, C.POINTER(_i32)
+_coupling_t = [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _vp]
+_spline_t = [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _f, _i32, _vp]
+_spline_bwd_t = [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _f, _i32, _vp]
+_conv1x1_t = [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp]
+_dsf_t = [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _vp]
+_ew_t = [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]
+_flow_t = [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _pi, _i32, _vp, _i64, _i32, _vp]
+_made_spline_t = [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _f, _i32, _vp]
+_ABI = {
+    "tfk_abi_version": (_int, []),
+    "tfk_last_error": (C.c_char_p, []),
+    "tfk_device_info": (_int, [C.c_char_p, _i32, _pi]),
+    "tfk_affine_coupling_fwd": (_int, _coupling_t),
+    "tfk_affine_coupling_inv": (_int, _coupling_t),
+    "tfk_shift_coupling_fwd": (_int, _coupling_t),
+    "tfk_shift_coupling_inv": (_int, _coupling_t),
+    "tfk_rqs_coupling_fwd": (_int, _spline_t),
+    "tfk_rqs_coupling_inv": (_int, _spline_t),
+    "tfk_conv1x1_coupling_fwd": (_int, _conv1x1_t),
+    "tfk_conv1x1_coupling_inv": (_int, _conv1x1_t),
+    "tfk_conv1x1_coupling_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp]),
+    "tfk_elementwise_affine_fwd": (_int, _ew_t),
+    "tfk_elementwise_affine_inv": (_int, _ew_t),
+    "tfk_permute": (_int, [_vp, _vp, _vp, _i64, _i32, _vp]),
+    "tfk_diag_gauss_logprob": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp]),
+    "tfk_sum_f32": (_int, [_vp, _vp, _i64, _vp]),
+    "tfk_sum_workspace_bytes": (_i64, [_i64]),
+    "tfk_sum_f32_ws": (_int, [_vp, _vp, _vp, _i64, _vp]),
+    "tfk_flow_supported": (_int, [_i32]),
+    "tfk_flow_run": (_int, _flow_t),
+    "tfk_flow_mfma_supported": (_int, [_i32]),
+    "tfk_flow_lean_supported": (_int, [_i32]),
+    "tfk_flow_run_mfma": (_int, _flow_t),
+    "tfk_flow_sum_workspace_bytes": (_i64, []),
+    "tfk_flow_run_mfma_sum": (_int, [_vp, _i32] + _flow_t[1:-1] + [_vp, _vp, _vp]),
+    "tfk_flow_run_mfma_ctx": (_int, [_vp, _vp, _i32] + _flow_t[1:]),
+    "tfk_flow_run_mfma_in": (_int, [_vp, _i32] + _flow_t[1:]),
+    "tfk_flow_wide_supported": (_int, [_i32, _i32]),
+    "tfk_flow_run_wide": (_int, _flow_t),
+    "tfk_lrs_coupling_fwd": (_int, _spline_t),
+    "tfk_lrs_coupling_inv": (_int, _spline_t),
+    "tfk_dsf_supported": (_int, [_i32, _i32]),
+    "tfk_dsf_coupling_fwd": (_int, _dsf_t),
+    "tfk_dsf_coupling_inv": (_int, _dsf_t),
+    "tfk_dsf_coupling_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "tfk_made_affine_sequential": (_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "tfk_made_rqs_sequential_lds_bytes": (_i64, [_i32, _i32, _i32]),
+    "tfk_made_rqs_sequential": (_int, _made_spline_t),
+    "tfk_made_lrs_sequential_lds_bytes": (_i64, [_i32, _i32, _i32]),
+    "tfk_made_lrs_sequential": (_int, _made_spline_t),
+    "tfk_conv3x3_block_supported": (_int, [_i32, _i32]),
+    "tfk_conv3x3_relu_pool_affine": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
+    "tfk_conv1x1_frame": (_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "tfk_bounded_sigmoid": (_int, [_vp, _vp, _i64, _f, _f, _vp]),
+    "tfk_bounded_sigmoid_bwd": (_int, [_vp, _vp, _vp, _i64, _f, _f, _vp]),
+    "tfk_convnet_train_workspace_bytes": (_i64, []),
+    "tfk_convnet_train_block_supported": (_int, [_i32, _i32, _i32]),
+    "tfk_convnet_train_block_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _i32, _i32, _vp, _vp,
+                                           _i64, _i32, _i32, _i32, _i32, _vp]),
+    "tfk_convnet_train_block_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i64,
+                                           _i32, _i32, _i32, _vp]),
+    "tfk_convnet_train_frame_fwd": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "tfk_convnet_train_frame_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _i32, _i32, _i32,
+                                           _i32, _i32, _i32, _i32, _i32, _vp]),
+    "tfk_convnet_train_forward": (_int, [C.POINTER(ConvNetTrainPlan), _vp, _vp, _i64, _i32, _i32, _vp]),
+    "tfk_convnet_train_sums_floats": (_i64, [_i32, _i32, _i32, _i32]),
+    "tfk_convnet_train_backward": (_int, [C.POINTER(ConvNetTrainPlan), _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp]),
+    "tfk_convnet_train_linear_prep": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "tfk_convnet_train_linear_fwd": (_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp]),
+    "tfk_convnet_train_linear_bwd_input": (_int, [_vp, _vp, _vp, _i64, _i32, _vp]),
+    "tfk_convnet_train_linear_wgrad": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
+    "tfk_glow_weight_floats": (_i64, [_i32]),
+    "tfk_glow_plan": (_int, [C.POINTER(GlowLayer), _i32, _pi, _pi, _pi, _pi, _pi, _pi]),
+    "tfk_glow_coupling": (_int, [_vp, _vp, _i64, _i32, C.POINTER(GlowLayer), _i32, _vp]),
+    "tfk_glow_level_blob_bytes": (_i64, [C.POINTER(GlowLevelStep), _i32, _i32, _i32, _i32, _i32]),
+    "tfk_glow_level_pack": (_int, [C.POINTER(GlowLevelStep), _i32, _i32, _i32, _i32, _i32, _vp, _i64]),
+    "tfk_glow_level_info": (_int, [_vp, _pi, _pi, _pi, _pi]),
+    "tfk_glow_level": (_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "tfk_rows_fma": (_int, [_vp, _vp, _i64, _i32, _vp]),
+    "tfk_rows_fma_gauss_logprob": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp]),
+    "tfk_affine_coupling_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _vp]),
+    "tfk_shift_coupling_bwd": (_int, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _vp]),
+    "tfk_rqs_coupling_bwd_supported": (_int, [_i32]),
+    "tfk_rqs_coupling_bwd": (_int, _spline_bwd_t),
+    "tfk_lrs_coupling_bwd": (_int, _spline_bwd_t),
+    "tfk_elementwise_affine_bwd_workspace_bytes": (_i64, [_i64, _i32]),
+    "tfk_elementwise_affine_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp]),
+    "tfk_diag_gauss_logprob_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp]),
+    "tfk_coupling_train_bwd_supported": (_int, [_i32]),
+    "tfk_coupling_train_bwd_out_floats": (_i64, [_i32]),
+    "tfk_coupling_train_bwd_workspace_bytes": (_i64, [_i32]),
+    "tfk_affine_coupling_train_bwd": (_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp]),
+    "tfk_rqs_coupling_train_bwd_supported": (_int, [_i32, _i32]),
+    "tfk_rqs_coupling_train_bwd": (_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _i32, _f, _i32, _vp, _i32, _vp]),
+    "tfk_rqs_coupling_train_bwd_hid": (_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _i32, _i32, _f, _i32, _vp, _i32,
+                                              _vp]),
+    "tfk_rows_outer_workspace_bytes": (_i64, [_i32]),
+    "tfk_rows_outer": (_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "tfk_wide_coupling_train_bwd_supported": (_int, [_i32, _i32]),
+    "tfk_wide_coupling_train_bwd_param_floats": (_i64, [_i32, _i32]),
+    "tfk_wide_coupling_train_bwd_grid_cap": (_i64, [_i32, _i32]),
+    "tfk_wide_coupling_train_bwd": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _i32, _vp]),
+}
+SYMBOLS = tuple(_ABI)        # every symbol include/tfk.h declares (tests check the built library exports all of them)
+
 _lib: Optional[C.CDLL] = None
 calls = 0   # number of kernel entry points invoked (tests assert the HIP path really ran)
 
@@ -117,127 +187,12 @@ def build(verbose: bool = False) -> str:
     return LIB_PATH
 
 
-def _bind(L: C.CDLL) -> None:
-    coupling = [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _vp]
-    for n in ("tfk_affine_coupling_fwd", "tfk_affine_coupling_inv",
-              "tfk_shift_coupling_fwd", "tfk_shift_coupling_inv"):
-        getattr(L, n).argtypes = coupling
-    rqs = [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32, C.c_float, _i32, _vp]
-    L.tfk_rqs_coupling_fwd.argtypes = rqs
-    L.tfk_rqs_coupling_inv.argtypes = rqs
-    L.tfk_lrs_coupling_fwd.argtypes = rqs
-    L.tfk_lrs_coupling_inv.argtypes = rqs
-    L.tfk_dsf_supported.argtypes = [_i32, _i32]
-    dsf = [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _vp]
-    L.tfk_dsf_coupling_fwd.argtypes = dsf
-    L.tfk_dsf_coupling_inv.argtypes = dsf
-    L.tfk_dsf_coupling_bwd.argtypes = [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _i32, _vp]
-    conv = [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp]
-    L.tfk_conv1x1_coupling_fwd.argtypes = conv
-    L.tfk_conv1x1_coupling_inv.argtypes = conv
-    L.tfk_conv1x1_coupling_bwd.argtypes = [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp]
-    ew = [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]
-    L.tfk_elementwise_affine_fwd.argtypes = ew
-    L.tfk_elementwise_affine_inv.argtypes = ew
-    L.tfk_permute.argtypes = [_vp, _vp, _vp, _i64, _i32, _vp]
-    L.tfk_diag_gauss_logprob.argtypes = [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp]
-    L.tfk_sum_workspace_bytes.argtypes = [_i64]
-    L.tfk_sum_workspace_bytes.restype = _i64
-    L.tfk_sum_f32.argtypes = [_vp, _vp, _i64, _vp]
-    L.tfk_sum_f32_ws.argtypes = [_vp, _vp, _vp, _i64, _vp]
-    L.tfk_flow_supported.argtypes = [_i32]
-    L.tfk_flow_run.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, C.POINTER(_i32), _i32,
-                               _vp, _i64, _i32, _vp]
-    L.tfk_flow_mfma_supported.argtypes = [_i32]
-    L.tfk_flow_lean_supported.argtypes = [_i32]
-    L.tfk_flow_run_mfma.argtypes = L.tfk_flow_run.argtypes
-    L.tfk_flow_run_mfma_in.argtypes = [_vp, _i32] + L.tfk_flow_run.argtypes[1:]
-    L.tfk_flow_run_mfma_ctx.argtypes = [_vp, _vp, _i32] + L.tfk_flow_run.argtypes[1:]
-    L.tfk_flow_sum_workspace_bytes.argtypes = []
-    L.tfk_flow_sum_workspace_bytes.restype = _i64
-    L.tfk_flow_run_mfma_sum.argtypes = [_vp, _i32] + L.tfk_flow_run.argtypes[1:-1] + [_vp, _vp, _vp]
-    L.tfk_flow_wide_supported.argtypes = [_i32, _i32]
-    L.tfk_flow_run_wide.argtypes = L.tfk_flow_run.argtypes
-    L.tfk_affine_coupling_bwd.argtypes = [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _vp]
-    L.tfk_shift_coupling_bwd.argtypes = [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _vp]
-    L.tfk_rqs_coupling_bwd_supported.argtypes = [_i32]
-    L.tfk_rqs_coupling_bwd.argtypes = [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32,
-                                       C.c_float, _i32, _vp]
-    L.tfk_lrs_coupling_bwd.argtypes = [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32,
-                                       C.c_float, _i32, _vp]
-    L.tfk_elementwise_affine_bwd_workspace_bytes.argtypes = [_i64, _i32]
-    L.tfk_elementwise_affine_bwd_workspace_bytes.restype = _i64
-    L.tfk_elementwise_affine_bwd.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp]
-    L.tfk_diag_gauss_logprob_bwd.argtypes = [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp]
-    L.tfk_coupling_train_bwd_supported.argtypes = [_i32]
-    L.tfk_coupling_train_bwd_out_floats.argtypes = [_i32]
-    L.tfk_coupling_train_bwd_out_floats.restype = _i64
-    L.tfk_coupling_train_bwd_workspace_bytes.argtypes = [_i32]
-    L.tfk_coupling_train_bwd_workspace_bytes.restype = _i64
-    L.tfk_affine_coupling_train_bwd.argtypes = [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _i32,
-                                                _vp, _i32, _vp]
-    L.tfk_rqs_coupling_train_bwd_supported.argtypes = [_i32, _i32]
-    L.tfk_rqs_coupling_train_bwd.argtypes = [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _i32,
-                                             C.c_float, _i32, _vp, _i32, _vp]
-    L.tfk_rqs_coupling_train_bwd_hid.argtypes = [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _i32, _i32,
-                                                 C.c_float, _i32, _vp, _i32, _vp]
-    L.tfk_rows_outer_workspace_bytes.argtypes = [_i32]
-    L.tfk_rows_outer_workspace_bytes.restype = _i64
-    L.tfk_rows_outer.argtypes = [_vp, _i32, _i32, _vp, _vp, _vp, _i64, _vp]
-    L.tfk_wide_coupling_train_bwd_supported.argtypes = [_i32, _i32]
-    L.tfk_wide_coupling_train_bwd_param_floats.argtypes = [_i32, _i32]
-    L.tfk_wide_coupling_train_bwd_param_floats.restype = _i64
-    L.tfk_wide_coupling_train_bwd_grid_cap.argtypes = [_i32, _i32]
-    L.tfk_wide_coupling_train_bwd_grid_cap.restype = _i64
-    L.tfk_wide_coupling_train_bwd.argtypes = [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp,
-                                              _i32, _vp]
-    L.tfk_made_affine_sequential.argtypes = [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]
-    L.tfk_made_rqs_sequential_lds_bytes.argtypes = [_i32, _i32, _i32]
-    L.tfk_made_rqs_sequential_lds_bytes.restype = _i64
-    L.tfk_made_rqs_sequential.argtypes = [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _i32, C.c_float, _i32, _vp]
-    L.tfk_made_lrs_sequential_lds_bytes.argtypes = [_i32, _i32, _i32]
-    L.tfk_made_lrs_sequential_lds_bytes.restype = _i64
-    L.tfk_made_lrs_sequential.argtypes = [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _i32, C.c_float, _i32, _vp]
-    L.tfk_conv3x3_block_supported.argtypes = [_i32, _i32]
-    L.tfk_conv3x3_relu_pool_affine.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]
-    L.tfk_bounded_sigmoid.argtypes = [_vp, _vp, _i64, C.c_float, C.c_float, _vp]
-    L.tfk_bounded_sigmoid_bwd.argtypes = [_vp, _vp, _vp, _i64, C.c_float, C.c_float, _vp]
-    L.tfk_conv1x1_frame.argtypes = [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp]
-    L.tfk_glow_weight_floats.argtypes = [_i32]
-    L.tfk_glow_weight_floats.restype = _i64
-    pi = C.POINTER(_i32)
-    L.tfk_glow_plan.argtypes = [C.POINTER(GlowLayer), _i32, pi, pi, pi, pi, pi, pi]
-    L.tfk_glow_coupling.argtypes = [_vp, _vp, _i64, _i32, C.POINTER(GlowLayer), _i32, _vp]
-    L.tfk_rows_fma.argtypes = [_vp, _vp, _i64, _i32, _vp]
-    L.tfk_rows_fma_gauss_logprob.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp]
-    ps = C.POINTER(GlowLevelStep)
-    L.tfk_glow_level_blob_bytes.argtypes = [ps, _i32, _i32, _i32, _i32, _i32]
-    L.tfk_glow_level_blob_bytes.restype = _i64
-    L.tfk_glow_level_pack.argtypes = [ps, _i32, _i32, _i32, _i32, _i32, _vp, _i64]
-    L.tfk_glow_level_info.argtypes = [_vp, pi, pi, pi, pi]
-    L.tfk_glow_level.argtypes = [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]
-    L.tfk_convnet_train_workspace_bytes.argtypes = []
-    L.tfk_convnet_train_workspace_bytes.restype = _i64
-    L.tfk_convnet_train_block_supported.argtypes = [_i32, _i32, _i32]
-    L.tfk_convnet_train_block_fwd.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_float, C.c_float,
-                                              _i32, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]
-    L.tfk_convnet_train_block_bwd.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp,
-                                              _i64, _i32, _i32, _i32, _vp]
-    L.tfk_convnet_train_frame_fwd.argtypes = [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
-                                              _vp]
-    L.tfk_convnet_train_frame_bwd.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _i32,
-                                              _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]
-    L.tfk_convnet_train_linear_wgrad.argtypes = [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]
-    L.tfk_convnet_train_linear_prep.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]
-    pp = C.POINTER(ConvNetTrainPlan)
-    L.tfk_convnet_train_forward.argtypes = [pp, _vp, _vp, _i64, _i32, _i32, _vp]
-    L.tfk_convnet_train_backward.argtypes = [pp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp]
-    L.tfk_convnet_train_sums_floats.argtypes = [_i32, _i32, _i32, _i32]
-    L.tfk_convnet_train_sums_floats.restype = _i64
-    L.tfk_convnet_train_linear_fwd.argtypes = [_vp, _vp, _vp, _vp, _i64, _i32, _vp]
-    L.tfk_convnet_train_linear_bwd_input.argtypes = [_vp, _vp, _vp, _i64, _i32, _vp]
-    L.tfk_last_error.restype = C.c_char_p
-    L.tfk_device_info.argtypes = [C.c_char_p, _i32, C.POINTER(_i32)]
+def bind(L: C.CDLL, names=None) -> None:
+    """Give the functions ``names`` of ``L`` (default: all of them) their prototypes from the table -- libtfk.so here, the
+    CPU restatement of the same ABI in tests/test_cabi_host.py."""
+    for name in (_ABI if names is None else names):
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = _ABI[name]
 
 
 def lib() -> C.CDLL:
@@ -257,7 +212,7 @@ def lib() -> C.CDLL:
             raise NativeError(f"{LIB_PATH} lacks symbols {missing}; rebuild it")
         if L.tfk_abi_version() != ABI_VERSION:
             raise NativeError(f"{LIB_PATH} has ABI {L.tfk_abi_version()}, expected {ABI_VERSION}")
-        _bind(L)
+        bind(L)
         _lib = L
     return _lib
 
@@ -301,9 +256,13 @@ def _ptr(t: Optional[torch.Tensor], what: str) -> Optional[int]:
 
 
 def _f32(t: Optional[torch.Tensor], what: str) -> Optional[int]:
-    if t is not None and t.dtype != torch.float32:
+    if t is None:
+        return None
+    if t.dtype != torch.float32:
         raise NativeError(f"{what}: expected float32, got {t.dtype}")
-    return _ptr(t, what)
+    if t.device.type != "cuda" or not t.is_contiguous():
+        return _ptr(t, what)                # (raises, with the reason)
+    return t.data_ptr()
 
 
 def _idx(t: Optional[torch.Tensor], what: str) -> Optional[int]:
@@ -349,49 +308,56 @@ def _rows(x: torch.Tensor, what: str):
     return x.shape[0], x.shape[1]
 
 
-def _coupling(name, x, h, out, logdet, tgt_idx, T, P, accumulate, extra=()):
+def _launch(name, anchor, *args, n=1):
+    """Enqueue entry point ``name`` on the current stream of ``anchor``'s device, that device made current; ``n``: how many
+    kernel entry points the call stands for in ``calls``."""
     global calls
+    fn = getattr(_lib if _lib is not None else lib(), name)
+    with _device_guard(anchor):
+        rc = fn(*args, _stream(anchor))
+    calls += n
+    if rc != 0:
+        _check(rc, name)
+
+
+def _coupling(name, x, h, out, logdet, tgt_idx, T, per_row, what, accumulate, extra=()):
+    """``per_row``: the parameters h holds per row, spelled ``what`` in the message (as in ``_coupling_bwd``)."""
     N, D = _rows(x, name)
     if out.shape != x.shape:
         raise NativeError(f"{name}: out shape {tuple(out.shape)} != x shape {tuple(x.shape)}")
-    if h.numel() != N * T * P:
-        raise NativeError(f"{name}: h has {h.numel()} elements, expected N*T*P = {N}*{T}*{P}")
+    if h.numel() != N * per_row:
+        raise NativeError(f"{name}: h has {h.numel()} elements, expected {what} = {N * per_row}")
     if logdet is not None and logdet.numel() != N:
         raise NativeError(f"{name}: logdet has {logdet.numel()} elements, expected {N}")
     if tgt_idx is not None and tgt_idx.numel() != T:
         raise NativeError(f"{name}: tgt_idx has {tgt_idx.numel()} entries, expected T = {T}")
-    fn = getattr(lib(), name)
-    args = (_f32(x, name), _f32(h, name), _f32(out, name), _f32(logdet, name), N, D,
+    _launch(name, x, _f32(x, name), _f32(h, name), _f32(out, name), _f32(logdet, name), N, D,
             _idx(tgt_idx, name), T, *extra, 1 if accumulate else 0)
-    with _device_guard(x):
-        rc = fn(*args, _stream(x))
-    calls += 1
-    _check(rc, name)
 
 
 def affine_coupling(x, h, out, logdet, tgt_idx, T, accumulate=False, inverse=False):
     """x, out: (N, D); h: (N, T, 2); logdet: (N,).  tgt_idx None = contiguous tail."""
     _coupling("tfk_affine_coupling_inv" if inverse else "tfk_affine_coupling_fwd",
-              x, h, out, logdet, tgt_idx, T, 2, accumulate)
+              x, h, out, logdet, tgt_idx, T, T * 2, "N*T*2", accumulate)
 
 
 def shift_coupling(x, h, out, logdet, tgt_idx, T, accumulate=False, inverse=False):
     _coupling("tfk_shift_coupling_inv" if inverse else "tfk_shift_coupling_fwd",
-              x, h, out, logdet, tgt_idx, T, 1, accumulate)
+              x, h, out, logdet, tgt_idx, T, T, "N*T", accumulate)
 
 
 def rqs_coupling(x, h, out, logdet, tgt_idx, T, n_bins, boundary, accumulate=False,
                  inverse=False):
     """h: (N, T, 3*n_bins - 1)."""
     _coupling("tfk_rqs_coupling_inv" if inverse else "tfk_rqs_coupling_fwd",
-              x, h, out, logdet, tgt_idx, T, 3 * n_bins - 1, accumulate,
+              x, h, out, logdet, tgt_idx, T, T * (3 * n_bins - 1), "N*T*P", accumulate,
               extra=(int(n_bins), C.c_float(float(boundary))))
 
 
 def lrs_coupling(x, h, out, logdet, tgt_idx, T, n_bins, boundary, accumulate=False, inverse=False):
     """Linear rational spline coupling; h: (N, T, 4*n_bins)."""
     _coupling("tfk_lrs_coupling_inv" if inverse else "tfk_lrs_coupling_fwd",
-              x, h, out, logdet, tgt_idx, T, 4 * n_bins, accumulate,
+              x, h, out, logdet, tgt_idx, T, T * 4 * n_bins, "N*T*P", accumulate,
               extra=(int(n_bins), C.c_float(float(boundary))))
 
 
@@ -403,73 +369,47 @@ def dsf_supported(n_components, hidden_dim) -> bool:
 def dsf_coupling(x, h, out, logdet, tgt_idx, T, n_components, hidden_dim, accumulate=False, inverse=False):
     """Deep sigmoidal coupling; h: (N, T, 3 * hidden_dim * n_components).  ``inverse``: the whole bisection in the launch."""
     _coupling("tfk_dsf_coupling_inv" if inverse else "tfk_dsf_coupling_fwd",
-              x, h, out, logdet, tgt_idx, T, 3 * int(hidden_dim) * int(n_components), accumulate,
+              x, h, out, logdet, tgt_idx, T, T * 3 * int(hidden_dim) * int(n_components), "N*T*P", accumulate,
               extra=(int(n_components), int(hidden_dim)))
 
 
 def conv1x1_coupling(x, h, out, logdet, tgt_idx, T, n_channels, accumulate=False, inverse=False):
     """Invertible 1x1 convolution on the T target positions (n_channels x T/n_channels pixels,
     channel-major); h: (N, n + n(n-1)) LU parameters per sample."""
-    global calls
     name = "tfk_conv1x1_coupling_inv" if inverse else "tfk_conv1x1_coupling_fwd"
-    N, D = _rows(x, name)
     n = int(n_channels)
-    if out.shape != x.shape or logdet.numel() != N or h.numel() != N * (n + n * (n - 1)):
-        raise NativeError(f"{name}: bad out / logdet / h shape")
-    if tgt_idx is not None and tgt_idx.numel() != T:
-        raise NativeError(f"{name}: tgt_idx has {tgt_idx.numel()} entries, expected T = {T}")
-    args = (_f32(x, name), _f32(h, name), _f32(out, name), _f32(logdet, name), N, D,
-            _idx(tgt_idx, name), T, n, 1 if accumulate else 0)
-    with _device_guard(x):
-        rc = getattr(lib(), name)(*args, _stream(x))
-    calls += 1
-    _check(rc, name)
+    _coupling(name, x, h, out, logdet, tgt_idx, T, n * n, "N * n^2", accumulate, extra=(n,))
 
 
 def elementwise_affine(x, value, out, logdet, inverse_affine, accumulate=False, inverse=False):
     """value: (D, 2) global parameters; inverse_affine selects the ActNorm transformer."""
-    global calls
     name = "tfk_elementwise_affine_inv" if inverse else "tfk_elementwise_affine_fwd"
     N, D = _rows(x, name)
     if value.numel() != 2 * D:
         raise NativeError(f"{name}: value has {value.numel()} elements, expected 2*D = {2 * D}")
     if out.shape != x.shape or logdet.numel() != N:
         raise NativeError(f"{name}: bad out/logdet shape")
-    args = (_f32(x, name), _f32(value, name), _f32(out, name), _f32(logdet, name), N, D,
+    _launch(name, x, _f32(x, name), _f32(value, name), _f32(out, name), _f32(logdet, name), N, D,
             1 if inverse_affine else 0, 1 if accumulate else 0)
-    with _device_guard(x):
-        rc = getattr(lib(), name)(*args, _stream(x))
-    calls += 1
-    _check(rc, name)
 
 
 def permute(x, perm, out):
     """out[n, j] = x[n, perm[j]]; perm None = reversal."""
-    global calls
-    N, D = _rows(x, "tfk_permute")
+    name = "tfk_permute"
+    N, D = _rows(x, name)
     if out.shape != x.shape:
         raise NativeError("tfk_permute: bad out shape")
     if perm is not None and perm.numel() != D:
         raise NativeError(f"tfk_permute: perm has {perm.numel()} entries, expected D = {D}")
-    args = (_f32(x, "tfk_permute"), _idx(perm, "tfk_permute"), _f32(out, "tfk_permute"), N, D)
-    with _device_guard(x):
-        rc = lib().tfk_permute(*args, _stream(x))
-    calls += 1
-    _check(rc, "tfk_permute")
+    _launch(name, x, _f32(x, name), _idx(perm, name), _f32(out, name), N, D)
 
 
 def diag_gauss_logprob(z, loc, log_scale, logdet_in, out):
-    global calls
     name = "tfk_diag_gauss_logprob"
     N, D = _rows(z, name)
     if loc.numel() != D or log_scale.numel() != D or out.numel() != N:
         raise NativeError(f"{name}: bad parameter/out shape")
-    args = (_f32(z, name), _f32(loc, name), _f32(log_scale, name), _f32(logdet_in, name),
-            _f32(out, name), N, D)
-    with _device_guard(z):
-        rc = lib().tfk_diag_gauss_logprob(*args, _stream(z))
-    calls += 1
-    _check(rc, name)
+    _launch(name, z, _f32(z, name), _f32(loc, name), _f32(log_scale, name), _f32(logdet_in, name), _f32(out, name), N, D)
 
 
 # ---- reverse mode (csrc/tfk_bwd.hip) ------------------------------------------------------
@@ -484,100 +424,148 @@ def _bwd_common(name, x, g, gld, tgt_idx, T):
     return N, D
 
 
+def _coupling_bwd(name, x, h, g, gld, gh, tgt_idx, T, per_row, what, extra, inverse):
+    """In place on g (N, D): target columns dL/d out -> dL/d x; gh, shaped like h (``per_row`` parameters a row, spelled
+    ``what`` in the message), written."""
+    N, D = _bwd_common(name, x, g, gld, tgt_idx, T)
+    if h.numel() != N * per_row or gh.numel() != N * per_row:
+        raise NativeError(f"{name}: h / gh must hold {what} = {N * per_row} elements")
+    _launch(name, g, _f32(x, name), _f32(h, name), _f32(g, name), _f32(gld, name), _f32(gh, name), N, D,
+            _idx(tgt_idx, name), T, *extra, 1 if inverse else 0)
+
+
 def affine_coupling_bwd(x, h, g, gld, gh, tgt_idx, T, inverse=False):
     """In place on g (N, D): target columns dL/d out -> dL/d x; gh (N, T, 2) written."""
-    global calls
-    name = "tfk_affine_coupling_bwd"
-    N, D = _bwd_common(name, x, g, gld, tgt_idx, T)
-    if h.numel() != N * T * 2 or gh.numel() != N * T * 2:
-        raise NativeError(f"{name}: h / gh must hold N*T*2 = {N * T * 2} elements")
-    args = (_f32(x, name), _f32(h, name), _f32(g, name), _f32(gld, name), _f32(gh, name), N, D,
-            _idx(tgt_idx, name), T, 1 if inverse else 0)
-    with _device_guard(g):
-        rc = lib().tfk_affine_coupling_bwd(*args, _stream(g))
-    calls += 1
-    _check(rc, name)
+    _coupling_bwd("tfk_affine_coupling_bwd", x, h, g, gld, gh, tgt_idx, T, T * 2, "N*T*2", (), inverse)
 
 
 def conv1x1_coupling_bwd(x, h, g, gld, gh, tgt_idx, T, n_channels, inverse=False):
     """Reverse mode of ``conv1x1_coupling``: in place on g (N, D) at the T target positions, gh (N, n + n(n-1)) written."""
-    global calls
-    name = "tfk_conv1x1_coupling_bwd"
-    N, D = _bwd_common(name, x, g, gld, tgt_idx, T)
     n = int(n_channels)
-    if h.numel() != N * n * n or gh.numel() != N * n * n:
-        raise NativeError(f"{name}: h / gh must hold N * n^2 = {N * n * n} elements")
-    args = (_f32(x, name), _f32(h, name), _f32(g, name), _f32(gld, name), _f32(gh, name), N, D,
-            _idx(tgt_idx, name), T, n, 1 if inverse else 0)
-    with _device_guard(g):
-        rc = lib().tfk_conv1x1_coupling_bwd(*args, _stream(g))
-    calls += 1
-    _check(rc, name)
+    _coupling_bwd("tfk_conv1x1_coupling_bwd", x, h, g, gld, gh, tgt_idx, T, n * n, "N * n^2", (n,), inverse)
 
 
 def shift_coupling_bwd(g, gh, tgt_idx, T, inverse=False):
-    global calls
     name = "tfk_shift_coupling_bwd"
     N, D = _bwd_common(name, None, g, None, tgt_idx, T)
     if gh.numel() != N * T:
         raise NativeError(f"{name}: gh must hold N*T = {N * T} elements")
-    args = (_f32(g, name), _f32(gh, name), N, D, _idx(tgt_idx, name), T, 1 if inverse else 0)
-    with _device_guard(g):
-        rc = lib().tfk_shift_coupling_bwd(*args, _stream(g))
-    calls += 1
-    _check(rc, name)
+    _launch(name, g, _f32(g, name), _f32(gh, name), N, D, _idx(tgt_idx, name), T, 1 if inverse else 0)
 
 
 def rqs_coupling_bwd(x, h, g, gld, gh, tgt_idx, T, n_bins, boundary, inverse=False):
-    global calls
-    name = "tfk_rqs_coupling_bwd"
-    N, D = _bwd_common(name, x, g, gld, tgt_idx, T)
-    P = 3 * int(n_bins) - 1
-    if h.numel() != N * T * P or gh.numel() != N * T * P:
-        raise NativeError(f"{name}: h / gh must hold N*T*P = {N * T * P} elements")
-    args = (_f32(x, name), _f32(h, name), _f32(g, name), _f32(gld, name), _f32(gh, name), N, D,
-            _idx(tgt_idx, name), T, int(n_bins), C.c_float(float(boundary)), 1 if inverse else 0)
-    with _device_guard(g):
-        rc = lib().tfk_rqs_coupling_bwd(*args, _stream(g))
-    calls += 1
-    _check(rc, name)
+    _coupling_bwd("tfk_rqs_coupling_bwd", x, h, g, gld, gh, tgt_idx, T, T * (3 * int(n_bins) - 1), "N*T*P",
+                  (int(n_bins), C.c_float(float(boundary))), inverse)
 
 
 def lrs_coupling_bwd(x, h, g, gld, gh, tgt_idx, T, n_bins, boundary, inverse=False):
-    global calls
-    name = "tfk_lrs_coupling_bwd"
-    N, D = _bwd_common(name, x, g, gld, tgt_idx, T)
-    P = 4 * int(n_bins)
-    if h.numel() != N * T * P or gh.numel() != N * T * P:
-        raise NativeError(f"{name}: h / gh must hold N*T*P = {N * T * P} elements")
-    args = (_f32(x, name), _f32(h, name), _f32(g, name), _f32(gld, name), _f32(gh, name), N, D,
-            _idx(tgt_idx, name), T, int(n_bins), C.c_float(float(boundary)), 1 if inverse else 0)
-    with _device_guard(g):
-        rc = lib().tfk_lrs_coupling_bwd(*args, _stream(g))
-    calls += 1
-    _check(rc, name)
+    _coupling_bwd("tfk_lrs_coupling_bwd", x, h, g, gld, gh, tgt_idx, T, T * 4 * int(n_bins), "N*T*P",
+                  (int(n_bins), C.c_float(float(boundary))), inverse)
 
 
 def dsf_coupling_bwd(x, h, g, gld, gh, tgt_idx, T, n_components, hidden_dim, inverse=False):
     """Reverse mode of ``dsf_coupling`` (forward direction only: the bisection carries no gradient)."""
-    global calls
-    name = "tfk_dsf_coupling_bwd"
-    N, D = _bwd_common(name, x, g, gld, tgt_idx, T)
-    P = 3 * int(hidden_dim) * int(n_components)
-    if h.numel() != N * T * P or gh.numel() != N * T * P:
-        raise NativeError(f"{name}: h / gh must hold N*T*P = {N * T * P} elements")
-    args = (_f32(x, name), _f32(h, name), _f32(g, name), _f32(gld, name), _f32(gh, name), N, D,
-            _idx(tgt_idx, name), T, int(n_components), int(hidden_dim), 1 if inverse else 0)
-    with _device_guard(g):
-        rc = lib().tfk_dsf_coupling_bwd(*args, _stream(g))
-    calls += 1
-    _check(rc, name)
+    _coupling_bwd("tfk_dsf_coupling_bwd", x, h, g, gld, gh, tgt_idx, T, T * 3 * int(hidden_dim) * int(n_components), "N*T*P",
+                  (int(n_components), int(hidden_dim)), inverse)
+
+
+# ---- the transformer kinds (``transformer.native_kind``): which wrappers serve each, with which scalar arguments, and when
+# there is a kernel -- what the layers (layers_base.py) and the training chain (autograd.py) ask instead of naming kinds.
+def _dsf_native(tr) -> bool:
+    """A deep sigmoidal transformer of a size csrc/tfk_dsf.hip is instantiated for (tfk_dsf_supported); other sizes --
+    and all of them under TORCHFLOWS_AMD_DEBUG="dsf=0" (comparison runs) -- take the ATen composite path."""
+    from torchflows_amd.utils import debug_switch
+    if debug_switch("dsf", "1") == "0":
+        return False
+    return dsf_supported(tr.n_components, tr.hidden_dim)
+
+
+def _always(tr) -> bool:
+    return True
+
+
+def _never(tr) -> bool:
+    return False
+
+
+def _rqs_bins(tr) -> bool:
+    return 2 <= tr.n_bins <= 32
+
+
+def _lrs_bins(tr) -> bool:
+    return int(tr.n_bins) in (4, 8)
+
+
+class TransformerKind(NamedTuple):
+    forward: str                # wrapper names, looked up in this module when called: a stubbed wrapper is what runs
+    reverse: str
+    scalars: Optional[Callable]  # transformer -> the wrappers' scalar arguments behind T (None: there are none)
+    flipped: bool               # the transformer's forward is the kernel's inverse form (InverseAffine)
+    coupling: Callable          # transformer -> is there a coupling kernel
+    made: Callable              # ... a parallel pass for a MADE layer of it
+    reverse_mode: Callable      # ... reverse-mode kernels
+    reverse_reads_x: bool = True   # the reverse wrapper takes (x, h, g, gld, gh, ...); a shift's only (g, gh, ...)
+
+
+KINDS = {
+    "affine": TransformerKind("affine_coupling", "affine_coupling_bwd", None, False, _always, _always, _always),
+    "inverse_affine": TransformerKind("affine_coupling", "affine_coupling_bwd", None, True, _always, _always, _always),
+    "shift": TransformerKind("shift_coupling", "shift_coupling_bwd", None, False, _always, _never, _always, False),
+    "rqs": TransformerKind("rqs_coupling", "rqs_coupling_bwd", attrgetter("n_bins", "boundary"), False, _rqs_bins, _rqs_bins,
+                           lambda tr: bool(lib().tfk_rqs_coupling_bwd_supported(int(tr.n_bins)))),
+    "lrs": TransformerKind("lrs_coupling", "lrs_coupling_bwd", attrgetter("n_bins", "boundary"), False, _lrs_bins, _lrs_bins, _lrs_bins),
+    "dsf": TransformerKind("dsf_coupling", "dsf_coupling_bwd", attrgetter("n_components", "hidden_dim"), False,
+                           _dsf_native, _dsf_native, _dsf_native),
+    "conv1x1": TransformerKind("conv1x1_coupling", "conv1x1_coupling_bwd", lambda tr: (tr.n_channels,), False,
+                               lambda tr: tr.n_channels <= 16,      # channels are kept in registers
+                               _never, lambda tr: int(tr.n_channels) <= 16),
+}
+
+
+def coupling_kernel(tr) -> bool:
+    """Is there a coupling kernel for this transformer?"""
+    kind = KINDS.get(tr.native_kind)
+    return kind is not None and bool(kind.coupling(tr))
+
+
+def made_kernel(tr) -> bool:
+    """... a parallel pass for a MADE layer of it?"""
+    kind = KINDS.get(tr.native_kind)
+    return kind is not None and bool(kind.made(tr))
+
+
+def reverse_kernel(tr) -> bool:
+    """... reverse-mode kernels?"""
+    kind = KINDS.get(tr.native_kind)
+    return kind is not None and bool(kind.reverse_mode(tr))
+
+
+def transform(tr, inverse, x, h, out, logdet, tgt, T, accumulate):
+    """The transformer's forward (``inverse``: inverse) map on the T target columns ``tgt`` (None: the tail) of x (N, D) with
+    the parameters ``h``."""
+    kind = KINDS.get(tr.native_kind)
+    if kind is None:
+        raise NativeError(f"no kernel for transformer kind {tr.native_kind!r}")
+    forward, _, scalars, flipped = kind[:4]
+    if scalars is None:
+        globals()[forward](x, h, out, logdet, tgt, T, accumulate=accumulate, inverse=inverse != flipped)
+    else:
+        globals()[forward](x, h, out, logdet, tgt, T, *scalars(tr), accumulate=accumulate, inverse=inverse != flipped)
+
+
+def transform_bwd(tr, inverse, x, h, g, gld, gh, tgt, T):
+    """Reverse mode of ``transform``: in place on ``g`` at the target columns, dL/dh written to ``gh``."""
+    kind = KINDS.get(tr.native_kind)
+    if kind is None:
+        raise NativeError(f"no kernel for transformer kind {tr.native_kind!r}")
+    extra = kind.scalars(tr) if kind.scalars is not None else ()
+    lead = (x, h, g, gld, gh) if kind.reverse_reads_x else (g, gh)
+    globals()[kind.reverse](*lead, tgt, T, *extra, inverse=inverse != kind.flipped)
 
 
 def elementwise_affine_bwd(x, value, g, gld, want_param, inverse=False, out=None):
     """In place on g (all D columns).  Returns dL/dvalue (D, 2) when ``want_param`` (written into ``out``, 2 D
     contiguous floats, when given)."""
-    global calls
     name = "tfk_elementwise_affine_bwd"
     N, D = _rows(g, name)
     if value.numel() != 2 * D:
@@ -591,34 +579,23 @@ def elementwise_affine_bwd(x, value, g, gld, want_param, inverse=False, out=None
         gvalue = torch.empty(D, 2, dtype=torch.float32, device=g.device) if out is None else out.view(D, 2)
         nbytes = int(lib().tfk_elementwise_affine_bwd_workspace_bytes(N, D))
         ws = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=g.device)
-    args = (_f32(x if want_param else None, name), _f32(value, name), _f32(g, name),
-            _f32(gld if want_param else None, name), _f32(gvalue, name), _f32(ws, name), N, D,
-            1 if inverse else 0)
-    with _device_guard(g):
-        rc = lib().tfk_elementwise_affine_bwd(*args, _stream(g))
-    calls += 1
-    _check(rc, name)
+    _launch(name, g, _f32(x if want_param else None, name), _f32(value, name), _f32(g, name),
+            _f32(gld if want_param else None, name), _f32(gvalue, name), _f32(ws, name), N, D, 1 if inverse else 0)
     return gvalue
 
 
 def diag_gauss_logprob_bwd(z, loc, log_scale, glp, g):
-    global calls
     name = "tfk_diag_gauss_logprob_bwd"
     N, D = _rows(z, name)
     if loc.numel() != D or log_scale.numel() != D or glp.numel() != N or g.shape != z.shape:
         raise NativeError(f"{name}: bad parameter / gradient shape")
-    args = (_f32(z, name), _f32(loc, name), _f32(log_scale, name), _f32(glp, name), _f32(g, name), N, D)
-    with _device_guard(z):
-        rc = lib().tfk_diag_gauss_logprob_bwd(*args, _stream(z))
-    calls += 1
-    _check(rc, name)
+    _launch(name, z, _f32(z, name), _f32(loc, name), _f32(log_scale, name), _f32(glp, name), _f32(g, name), N, D)
 
 
 def affine_coupling_train_bwd(x, g, gld, params, gemm2_steps, out, workspace, inverse_form=False,
                               gscale=None, g_reversed=False):
     """Fused conditioner + transform + MLP backward of one HalfSplit affine coupling (in place on
     g, accumulator-layout weight gradients into ``out``)."""
-    global calls
     name = "tfk_affine_coupling_train_bwd"
     N, D = _rows(g, name)
     if x.shape != g.shape or gld.numel() != N:
@@ -632,10 +609,7 @@ def affine_coupling_train_bwd(x, g, gld, params, gemm2_steps, out, workspace, in
             _f32(gscale, name), 1 if g_reversed else 0)
     if gscale is not None and gscale.numel() != D:
         raise NativeError(f"{name}: gscale must hold D = {D} floats")
-    with _device_guard(g):
-        rc = lib().tfk_affine_coupling_train_bwd(*args, _stream(g))
-    calls += 1
-    _check(rc, name)
+    _launch(name, g, *args)
 
 
 def rqs_coupling_train_bwd(x, g, gld, params, gemm2_steps, gh_perm, gpre_perm, n_bins, boundary,
@@ -643,7 +617,6 @@ def rqs_coupling_train_bwd(x, g, gld, params, gemm2_steps, gh_perm, gpre_perm, n
     """Conditioner re-evaluation + RQ-spline backward + dL/dhidden + dL/dx_A in one launch (in place on
     g); gh_perm (N, 768) and gpre_perm (N, 16) in accumulator order; ``hid_perm`` (N, 16): also the hidden activations,
     column 15 == 1 (tfk_rqs_coupling_train_bwd_hid)."""
-    global calls
     name = "tfk_rqs_coupling_train_bwd" if hid_perm is None else "tfk_rqs_coupling_train_bwd_hid"
     N, D = _rows(g, name)
     if x.shape != g.shape or gld.numel() != N or gh_perm.shape != (N, 768) or gpre_perm.shape != (N, 16):
@@ -655,13 +628,8 @@ def rqs_coupling_train_bwd(x, g, gld, params, gemm2_steps, gh_perm, gpre_perm, n
     head = (_f32(x, name), _f32(g, name), _f32(gld, name), _f32(params, name), params.numel(),
             int(gemm2_steps), _f32(gh_perm, name), _f32(gpre_perm, name))
     tail = (N, D, int(n_bins), C.c_float(float(boundary)), 1 if inverse else 0, _f32(gscale, name), 1 if g_reversed else 0)
-    with _device_guard(g):
-        if hid_perm is None:
-            rc = lib().tfk_rqs_coupling_train_bwd(*head, *tail, _stream(g))
-        else:
-            rc = lib().tfk_rqs_coupling_train_bwd_hid(*head, _f32(hid_perm, name), *tail, _stream(g))
-    calls += 1
-    _check(rc, name)
+    hid = () if hid_perm is None else (_f32(hid_perm, name),)
+    _launch(name, g, *head, *hid, *tail)
 
 
 _rows_outer_ws = {}
@@ -695,17 +663,12 @@ def _rows_outer_workspace(device, M: int, stream: int):
 def rows_outer(A, M, B, out):
     """out[M * 16] (accumulator order, include/tfk.h) = sum over the rows of A[n, :M]^T B[n, :16] (tfk_rows_outer):
     the weight-gradient products that contract over the batch rows, deterministic, no GEMM-library call."""
-    global calls
     name = "tfk_rows_outer"
     N, lda = _rows(A, name)
     if B.shape != (N, 16) or out.numel() != M * 16 or not out.is_contiguous():
         raise NativeError(f"{name}: B must be (N, 16) and out hold M * 16 = {M * 16} contiguous floats")
     ws = _rows_outer_workspace(A.device, int(M), _stream(A))
-    with _device_guard(A):
-        rc = lib().tfk_rows_outer(_f32(A, name), int(lda), int(M), _f32(B, name), _f32(out, name), _f32(ws, name), N,
-                                  _stream(A))
-    calls += 1
-    _check(rc, name)
+    _launch(name, A, _f32(A, name), int(lda), int(M), _f32(B, name), _f32(out, name), _f32(ws, name), N)
 
 
 def wide_coupling_train_bwd(x, g, gld, params, gh_rec, gpre_rec, hid_rec, shift=False, inverse_form=False,
@@ -714,7 +677,6 @@ def wide_coupling_train_bwd(x, g, gld, params, gh_rec, gpre_rec, hid_rec, shift=
     in place on g; gh_rec (N, 2 hp) -- (N, hp) for a shift coupling --, gpre_rec (N, 16) and hid_rec (N, 16) are the records
     tfk_rows_outer contracts over the batch rows (include/tfk.h).  The records may be longer than N rows (buffers kept
     across steps): only the first N are written."""
-    global calls
     name = "tfk_wide_coupling_train_bwd"
     N, D = _rows(g, name)
     hp = (D // 2 + 63) // 64 * 64
@@ -728,52 +690,38 @@ def wide_coupling_train_bwd(x, g, gld, params, gh_rec, gpre_rec, hid_rec, shift=
     args = (_f32(x, name), _f32(g, name), _f32(gld, name), _f32(params, name), params.numel(), _f32(gh_rec, name),
             _f32(gpre_rec, name), _f32(hid_rec, name), N, D, 1 if shift else 0, 1 if inverse_form else 0,
             _f32(gscale, name), 1 if g_reversed else 0)
-    with _device_guard(g):
-        rc = lib().tfk_wide_coupling_train_bwd(*args, _stream(g))
-    calls += 1
-    _check(rc, name)
+    _launch(name, g, *args)
 
 
 def made_affine_sequential(z, out, logdet, W1t, b1, W2, b2, divide, accumulate=False):
     """The sequential map of a MADE-based affine layer in one launch; W1t (D, HP), b1 (HP,),
     W2 (D, 2, HP), b2 (D, 2) masked and zero-padded to HP hidden units."""
-    global calls
     name = "tfk_made_affine_sequential"
     N, D = _rows(z, name)
     HP = b1.numel()
     if out.shape != z.shape or logdet.numel() != N or W1t.numel() != D * HP or W2.numel() != 2 * D * HP \
             or b2.numel() != 2 * D:
         raise NativeError(f"{name}: bad tensor shapes")
-    args = (_f32(z, name), _f32(out, name), _f32(logdet, name), N, D, _f32(W1t, name), _f32(b1, name),
+    _launch(name, z, _f32(z, name), _f32(out, name), _f32(logdet, name), N, D, _f32(W1t, name), _f32(b1, name),
             _f32(W2, name), _f32(b2, name), HP, 1 if divide else 0, 1 if accumulate else 0)
-    with _device_guard(z):
-        rc = lib().tfk_made_affine_sequential(*args, _stream(z))
-    calls += 1
-    _check(rc, name)
 
 
 def made_rqs_sequential(z, out, logdet, W1t, b1, W2, b2, n_bins, boundary, accumulate=False, lrs=False):
     """The sequential map of a MADE-based RQ-spline (or, ``lrs``, linear-rational-spline) layer in one
     launch; W1t (D, HP), b1 (HP,), W2 (D, P, HP), b2 (D, P) masked and zero-padded to HP hidden units,
     P = 3 n_bins - 1 (RQ) or 4 n_bins (LRS)."""
-    global calls
     name = "tfk_made_lrs_sequential" if lrs else "tfk_made_rqs_sequential"
     N, D = _rows(z, name)
     HP, P = b1.numel(), (4 * int(n_bins) if lrs else 3 * int(n_bins) - 1)
     if out.shape != z.shape or logdet.numel() != N or W1t.numel() != D * HP or W2.numel() != P * D * HP \
             or b2.numel() != P * D:
         raise NativeError(f"{name}: bad tensor shapes")
-    args = (_f32(z, name), _f32(out, name), _f32(logdet, name), N, D, _f32(W1t, name), _f32(b1, name),
+    _launch(name, z, _f32(z, name), _f32(out, name), _f32(logdet, name), N, D, _f32(W1t, name), _f32(b1, name),
             _f32(W2, name), _f32(b2, name), HP, int(n_bins), C.c_float(float(boundary)), 1 if accumulate else 0)
-    with _device_guard(z):
-        rc = getattr(lib(), name)(*args, _stream(z))
-    calls += 1
-    _check(rc, name)
 
 
 def conv3x3_relu_pool_affine(x, weight, bias, scale, shift):
     """conv3x3(pad 1) -> ReLU -> MaxPool2d(2) -> per-channel scale / shift in one launch (NCHW)."""
-    global calls
     name = "tfk_conv3x3_relu_pool_affine"
     if x.dim() != 4 or weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or weight.shape[1] != x.shape[1]:
         raise NativeError(f"{name}: x (N, C, H, W) and weight (C_out, C, 3, 3) expected")
@@ -782,44 +730,30 @@ def conv3x3_relu_pool_affine(x, weight, bias, scale, shift):
     if bias.numel() != c_out or scale.numel() != c_out or shift.numel() != c_out:
         raise NativeError(f"{name}: bias / scale / shift must hold c_out = {c_out} values")
     out = torch.empty(N, c_out, H // 2, W // 2, dtype=torch.float32, device=x.device)
-    args = (_f32(x, name), _f32(weight, name), _f32(bias, name), _f32(scale, name), _f32(shift, name),
+    _launch(name, x, _f32(x, name), _f32(weight, name), _f32(bias, name), _f32(scale, name), _f32(shift, name),
             _f32(out, name), N, c_in, c_out, H, W)
-    with _device_guard(x):
-        rc = lib().tfk_conv3x3_relu_pool_affine(*args, _stream(x))
-    calls += 1
-    _check(rc, name)
     return out
 
 
 def bounded_sigmoid(h: torch.Tensor, lo: float, hi: float) -> torch.Tensor:
     """``lo + (hi - lo) * sigmoid(h)`` in one pass (ATen: three kernels, two temporaries)."""
-    global calls
     name = "tfk_bounded_sigmoid"
     out = torch.empty_like(h)
-    with _device_guard(h):
-        rc = lib().tfk_bounded_sigmoid(_f32(h, name), _f32(out, name), h.numel(), float(lo), float(hi), _stream(h))
-    calls += 1
-    _check(rc, name)
+    _launch(name, h, _f32(h, name), _f32(out, name), h.numel(), float(lo), float(hi))
     return out
 
 
 def bounded_sigmoid_bwd(out: torch.Tensor, g: torch.Tensor, lo: float, hi: float) -> torch.Tensor:
     """d(loss)/dh of ``out = lo + (hi - lo) * sigmoid(h)`` from ``out`` and d(loss)/d(out), one pass."""
-    global calls
     name = "tfk_bounded_sigmoid_bwd"
     g_in = torch.empty_like(out)
-    with _device_guard(out):
-        rc = lib().tfk_bounded_sigmoid_bwd(_f32(out, name), _f32(g, name), _f32(g_in, name), out.numel(), float(lo),
-                                           float(hi), _stream(out))
-    calls += 1
-    _check(rc, name)
+    _launch(name, out, _f32(out, name), _f32(g, name), _f32(g_in, name), out.numel(), float(lo), float(hi))
     return g_in
 
 
 def conv1x1_frame(x, weight, bias, h_out: int, w_out: int):
     """1x1 convolution c_in -> c_out placed in the middle of an (h_out, w_out) frame that holds the bias.
     ``x`` (N, C, H, W) may be a view whose images are contiguous but further apart than C*H*W."""
-    global calls
     name = "tfk_conv1x1_frame"
     if x.dim() != 4 or x.dtype != torch.float32 or x.device.type != "cuda":
         raise NativeError(f"{name}: x must be a float32 (N, C, H, W) tensor on a HIP device")
@@ -831,11 +765,8 @@ def conv1x1_frame(x, weight, bias, h_out: int, w_out: int):
         raise NativeError(f"{name}: weight (c_out, c_in[, 1, 1]) and bias (c_out,) expected")
     x_stride = x.stride(0) if N > 1 else c_in * H * W
     out = torch.empty(N, c_out, h_out, w_out, dtype=torch.float32, device=x.device)
-    with _device_guard(x):
-        rc = lib().tfk_conv1x1_frame(x.data_ptr(), x_stride, _f32(weight, name), _f32(bias, name), _f32(out, name),
-                                     N, c_in, c_out, H, W, h_out, w_out, _stream(x))
-    calls += 1
-    _check(rc, name)
+    _launch(name, x, x.data_ptr(), x_stride, _f32(weight, name), _f32(bias, name), _f32(out, name),
+            N, c_in, c_out, H, W, h_out, w_out)
     return out
 
 
@@ -863,7 +794,6 @@ def convnet_train_forward(plan: "ConvNetTrainPlan", params, bns, x, training: bo
     """The whole ConvNet conditioner in ONE call (tfk_convnet_train_forward): fills ``plan`` from ``params`` (the 18
     tensors in convnet_train._params order), the three BatchNorm modules and fresh activation buffers; returns (theta,
     acts, amax) -- the two buffers are what the backward call needs besides ``plan``."""
-    global calls
     name = "tfk_convnet_train_forward"
     N, c, h, w = x.shape
     (w_m1, b_m1, w1, b1, g1, be1, w2, b2, g2, be2, w3, b3, g3, be3, w_m2, b_m2, w_lin, b_lin) = params
@@ -897,18 +827,14 @@ def convnet_train_forward(plan: "ConvNetTrainPlan", params, bns, x, training: bo
     ab = amax.data_ptr()
     p.amax[0], p.amax[1], p.amax[2] = ab, ab + N * 2048, ab + N * (2048 + 512)
     p.workspace = convnet_train_workspace(x).data_ptr()
-    with _device_guard(x):
-        rc = lib().tfk_convnet_train_forward(C.byref(p), _f32(x, name), theta.data_ptr(), N, 1 if training else 0,
-                                             1 if update_running else 0, _stream(x))
-    calls += 7
-    _check(rc, name)
+    _launch(name, x, C.byref(p), _f32(x, name), theta.data_ptr(), N, 1 if training else 0, 1 if update_running else 0,
+            n=7)      # (seven kernel launches behind the one FFI crossing)
     return theta, acts, amax
 
 
 def convnet_train_backward(plan: "ConvNetTrainPlan", x, g_theta, training: bool):
     """The reverse pass of the whole network in ONE call (tfk_convnet_train_backward; ``plan`` as the forward call left it,
     its buffers alive): (g_x, bn_out (100 floats), sums) -- the layout of ``sums`` is in include/tfk.h."""
-    global calls
     name = "tfk_convnet_train_backward"
     N = x.shape[0]
     p = plan
@@ -917,11 +843,8 @@ def convnet_train_backward(plan: "ConvNetTrainPlan", x, g_theta, training: bool)
     scratch = torch.empty(N * CONVNET_SCRATCH_FLOATS, dtype=torch.float32, device=x.device)
     out = torch.empty(100 + n_sums, dtype=torch.float32, device=x.device)     # (its slices become the .grad tensors)
     base = out.data_ptr()
-    with _device_guard(x):
-        rc = lib().tfk_convnet_train_backward(C.byref(p), _f32(x, name), _f32(g_theta, name), g_x.data_ptr(),
-                                              scratch.data_ptr(), base, base + 400, N, 1 if training else 0, _stream(x))
-    calls += 7
-    _check(rc, name)
+    _launch(name, x, C.byref(p), _f32(x, name), _f32(g_theta, name), g_x.data_ptr(), scratch.data_ptr(), base, base + 400, N,
+            1 if training else 0, n=7)
     return g_x, out[:100], out[100:]
 
 
@@ -929,7 +852,6 @@ def convnet_train_block_fwd(x, in_affine, weight, bias, bn, training: bool, upda
     """One ConvNetBlock (conv3x3 -> ReLU -> MaxPool2d(2)) ahead of its BatchNorm ``bn``: returns (y before
     normalisation, argmax bytes, stats = scale | shift | mean | 1/std of that BatchNorm); ``in_affine``: the scale | shift
     of the BatchNorm in front of the block (applied on load) or None."""
-    global calls
     name = "tfk_convnet_train_block_fwd"
     N, c_in, H, W = x.shape
     c_out = weight.shape[0]
@@ -939,21 +861,16 @@ def convnet_train_block_fwd(x, in_affine, weight, bias, bn, training: bool, upda
     nb = bn.num_batches_tracked
     momentum = 0.0 if bn.momentum is None else float(bn.momentum)
     ws = convnet_train_workspace(x)
-    with _device_guard(x):
-        rc = lib().tfk_convnet_train_block_fwd(
-            _f32(x, name), _f32(in_affine, name), _f32(weight, name), _f32(bias, name), _f32(y, name), amax.data_ptr(),
+    _launch(name, x, _f32(x, name), _f32(in_affine, name), _f32(weight, name), _f32(bias, name), _f32(y, name), amax.data_ptr(),
             _f32(bn.weight, name), _f32(bn.bias, name), _f32(bn.running_mean, name), _f32(bn.running_var, name),
             None if nb is None else nb.data_ptr(), float(bn.eps), momentum, 1 if training else 0,
-            1 if update_running else 0, _f32(stats, name), ws.data_ptr(), N, c_in, c_out, H, W, _stream(x))
-    calls += 1
-    _check(rc, name)
+            1 if update_running else 0, _f32(stats, name), ws.data_ptr(), N, c_in, c_out, H, W)
     return y, amax, stats
 
 
 def convnet_train_block_bwd(gz, coef, y, amax, x, in_affine, weight, bn_stats, bn_training: bool):
     """Reverse mode of the block: returns (g_in, weight gradient, bias gradient, and -- when the input came through a
     BatchNorm with ``bn_stats`` -- (coef, d weight, d bias) of that BatchNorm, else None)."""
-    global calls
     name = "tfk_convnet_train_block_bwd"
     N, c_in, H, _ = x.shape
     c_out = weight.shape[0]
@@ -963,15 +880,11 @@ def convnet_train_block_bwd(gz, coef, y, amax, x, in_affine, weight, bn_stats, b
     if bn_stats is not None:
         bnout = torch.empty(5 * c_in, dtype=torch.float32, device=x.device)
     ws = convnet_train_workspace(x)
-    with _device_guard(x):
-        rc = lib().tfk_convnet_train_block_bwd(
-            _f32(gz, name), _f32(coef, name), _f32(y, name), amax.data_ptr(), _f32(x, name), _f32(in_affine, name),
+    _launch(name, x, _f32(gz, name), _f32(coef, name), _f32(y, name), amax.data_ptr(), _f32(x, name), _f32(in_affine, name),
             _f32(weight, name), _f32(g_in, name), _f32(sums, name), _f32(bn_stats, name),
             None if bnout is None else bnout.data_ptr(), None if bnout is None else bnout[3 * c_in:].data_ptr(),
             None if bnout is None else bnout[4 * c_in:].data_ptr(), 1 if bn_training else 0, ws.data_ptr(), N, c_in,
-            c_out, H, _stream(x))
-    calls += 1
-    _check(rc, name)
+            c_out, H)
     dW, db = sums[:c_out * c_in * 9].view(c_out, c_in, 3, 3), sums[c_out * c_in * 9:]
     prev = None if bnout is None else (bnout[:3 * c_in], bnout[3 * c_in:4 * c_in], bnout[4 * c_in:])
     return g_in, dW, db, prev
@@ -979,23 +892,18 @@ def convnet_train_block_bwd(gz, coef, y, amax, x, in_affine, weight, bn_stats, b
 
 def convnet_train_frame_fwd(x, in_affine, weight, bias, h_out: int, w_out: int):
     """ConvModifier (weight (c_out, c_in, kh, kw), kh / kw 1 or 2), the BatchNorm in front applied on load."""
-    global calls
     name = "tfk_convnet_train_frame_fwd"
     N, c_in, H, W = x.shape
     c_out, _, kh, kw = weight.shape
     out = torch.empty(N, c_out, h_out, w_out, dtype=torch.float32, device=x.device)
-    with _device_guard(x):
-        rc = lib().tfk_convnet_train_frame_fwd(_f32(x, name), _f32(in_affine, name), _f32(weight, name), _f32(bias, name),
-                                               _f32(out, name), N, c_in, c_out, H, W, h_out, w_out, kh, kw, _stream(x))
-    calls += 1
-    _check(rc, name)
+    _launch(name, x, _f32(x, name), _f32(in_affine, name), _f32(weight, name), _f32(bias, name), _f32(out, name),
+            N, c_in, c_out, H, W, h_out, w_out, kh, kw)
     return out
 
 
 def convnet_train_frame_bwd(g_out, x, in_affine, weight, bn_stats, bn_training: bool):
     """Reverse mode of the ConvModifier: (g_in, weight gradient (c_out, c_in, kh, kw), bias gradient (c_out), BatchNorm
     triple or None as in ``convnet_train_block_bwd``)."""
-    global calls
     name = "tfk_convnet_train_frame_bwd"
     N, c_in, H, W = x.shape
     _, c_out, h_out, w_out = g_out.shape
@@ -1008,14 +916,10 @@ def convnet_train_frame_bwd(g_out, x, in_affine, weight, bn_stats, bn_training: 
     if bn_stats is not None:
         bnout = torch.empty(5 * c_in, dtype=torch.float32, device=x.device)
     ws = convnet_train_workspace(x)
-    with _device_guard(x):
-        rc = lib().tfk_convnet_train_frame_bwd(
-            _f32(g_out, name), _f32(x, name), _f32(in_affine, name), _f32(weight, name), _f32(g_in, name),
+    _launch(name, x, _f32(g_out, name), _f32(x, name), _f32(in_affine, name), _f32(weight, name), _f32(g_in, name),
             _f32(sums, name), _f32(bn_stats, name), None if bnout is None else bnout.data_ptr(),
             None if bnout is None else bnout[3 * c_in:].data_ptr(), None if bnout is None else bnout[4 * c_in:].data_ptr(),
-            1 if bn_training else 0, ws.data_ptr(), N, c_in, c_out, H, W, h_out, w_out, kh, kw, _stream(x))
-    calls += 1
-    _check(rc, name)
+            1 if bn_training else 0, ws.data_ptr(), N, c_in, c_out, H, W, h_out, w_out, kh, kw)
     prev = None if bnout is None else (bnout[:3 * c_in], bnout[3 * c_in:4 * c_in], bnout[4 * c_in:])
     return g_in, sums[:K0].view(c_out, c_in, kh, kw), sums[K1:], prev
 
@@ -1023,60 +927,41 @@ def convnet_train_frame_bwd(g_out, x, in_affine, weight, bn_stats, bn_training: 
 def convnet_train_linear_prep(weight, bias, frame_bias, h_out: int, w_out: int):
     """The Linear layer behind the second ConvModifier folded to its 16 interior inputs: (W16 (M, 16), b_eff (M), w_frame
     (M)); weight (M, h_out * w_out), ``frame_bias`` the modifier's bias (1 element)."""
-    global calls
     name = "tfk_convnet_train_linear_prep"
     M = weight.shape[0]
     buf = torch.empty(M * 18, dtype=torch.float32, device=weight.device)
     W16, b_eff, w_frame = buf[:M * 16].view(M, 16), buf[M * 16:M * 17], buf[M * 17:]
-    with _device_guard(weight):
-        rc = lib().tfk_convnet_train_linear_prep(_f32(weight, name), _f32(bias, name), _f32(frame_bias, name),
-                                                 W16.data_ptr(), b_eff.data_ptr(), w_frame.data_ptr(), M, h_out, w_out,
-                                                 _stream(weight))
-    calls += 1
-    _check(rc, name)
+    _launch(name, weight, _f32(weight, name), _f32(bias, name), _f32(frame_bias, name), W16.data_ptr(), b_eff.data_ptr(),
+            w_frame.data_ptr(), M, h_out, w_out)
     return W16, b_eff, w_frame
 
 
 def convnet_train_linear_fwd(a16, W16, b_eff):
     """b_eff + a16 (N, 16) W16 (M, 16)^T -> (N, M)."""
-    global calls
     name = "tfk_convnet_train_linear_fwd"
     N, M = a16.shape[0], W16.shape[0]
     out = torch.empty(N, M, dtype=torch.float32, device=a16.device)
-    with _device_guard(a16):
-        rc = lib().tfk_convnet_train_linear_fwd(_f32(a16, name), W16.data_ptr(), b_eff.data_ptr(), _f32(out, name), N, M,
-                                                _stream(a16))
-    calls += 1
-    _check(rc, name)
+    _launch(name, a16, _f32(a16, name), W16.data_ptr(), b_eff.data_ptr(), _f32(out, name), N, M)
     return out
 
 
 def convnet_train_linear_bwd_input(g, W16):
     """g (N, M) W16 (M, 16) -> (N, 16)."""
-    global calls
     name = "tfk_convnet_train_linear_bwd_input"
     N, M = g.shape
     g16 = torch.empty(N, 16, dtype=torch.float32, device=g.device)
-    with _device_guard(g):
-        rc = lib().tfk_convnet_train_linear_bwd_input(_f32(g, name), W16.data_ptr(), _f32(g16, name), N, M, _stream(g))
-    calls += 1
-    _check(rc, name)
+    _launch(name, g, _f32(g, name), W16.data_ptr(), _f32(g16, name), N, M)
     return g16
 
 
 def convnet_train_linear_wgrad(g, a16, frame_bias, h_out: int, w_out: int):
     """(dW (M, h_out * w_out), db (M)) of the Linear layer behind the second ConvModifier, whose input equals
     ``frame_bias`` outside the 4 x 4 interior a16 (N, 16)."""
-    global calls
     name = "tfk_convnet_train_linear_wgrad"
     N, M = g.shape
     dW = torch.empty(M, h_out * w_out, dtype=torch.float32, device=g.device)
     db = torch.empty(M, dtype=torch.float32, device=g.device)
-    with _device_guard(g):
-        rc = lib().tfk_convnet_train_linear_wgrad(_f32(g, name), _f32(a16, name), _f32(frame_bias, name), _f32(dW, name),
-                                                  _f32(db, name), N, M, h_out, w_out, _stream(g))
-    calls += 1
-    _check(rc, name)
+    _launch(name, g, _f32(g, name), _f32(a16, name), _f32(frame_bias, name), _f32(dW, name), _f32(db, name), N, M, h_out, w_out)
     return dW, db
 
 
@@ -1115,24 +1000,31 @@ def _n_ops(ops) -> int:
     return len(ops) // 8 if isinstance(ops, C.Array) else len(ops)
 
 
+def _flow_sizes(name, N, D, gauss_width, z, logdet, logprob, gauss_loc, gauss_log_scale):
+    """The element counts the tfk_flow_run family asks of its optional outputs and of the base-density parameters (spelled
+    out: no tuples are built on the launch path)."""
+    if z is not None and z.numel() != N * D:
+        raise NativeError(f"{name}: tensor with {z.numel()} elements, expected {N * D}")
+    if logdet is not None and logdet.numel() != N:
+        raise NativeError(f"{name}: tensor with {logdet.numel()} elements, expected {N}")
+    if logprob is not None and logprob.numel() != N:
+        raise NativeError(f"{name}: tensor with {logprob.numel()} elements, expected {N}")
+    if gauss_loc is not None and gauss_loc.numel() != gauss_width:
+        raise NativeError(f"{name}: tensor with {gauss_loc.numel()} elements, expected {gauss_width}")
+    if gauss_log_scale is not None and gauss_log_scale.numel() != gauss_width:
+        raise NativeError(f"{name}: tensor with {gauss_log_scale.numel()} elements, expected {gauss_width}")
+
+
 def flow_run(x, z, logdet, gauss_loc, gauss_log_scale, logprob, ops, params, accumulate=False):
     """Fused flow program (tfk_flow_run).  ops: list of (kind, src_plane, H, offset[, K,
     boundary, scale, c]) tuples (host side), params: fp32 device block.  z / logdet / logprob
     may be None."""
-    global calls
     name = "tfk_flow_run"
     N, D = _rows(x, name)
     ops_arr = _pack_ops(ops)
-    for t, n in ((z, N * D), (logdet, N), (logprob, N), (gauss_loc, D), (gauss_log_scale, D)):
-        if t is not None and t.numel() != n:
-            raise NativeError(f"{name}: tensor with {t.numel()} elements, expected {n}")
-    args = (_f32(x, name), _f32(z, name), _f32(logdet, name), _f32(gauss_loc, name),
-            _f32(gauss_log_scale, name), _f32(logprob, name), N, D, ops_arr, _n_ops(ops),
-            _f32(params, name), params.numel(), 1 if accumulate else 0)
-    with _device_guard(x):
-        rc = lib().tfk_flow_run(*args, _stream(x))
-    calls += 1
-    _check(rc, name)
+    _flow_sizes(name, N, D, D, z, logdet, logprob, gauss_loc, gauss_log_scale)
+    _launch(name, x, _f32(x, name), _f32(z, name), _f32(logdet, name), _f32(gauss_loc, name), _f32(gauss_log_scale, name),
+            _f32(logprob, name), N, D, ops_arr, _n_ops(ops), _f32(params, name), params.numel(), 1 if accumulate else 0)
 
 
 def _stream_flag() -> int:
@@ -1159,75 +1051,28 @@ def flow_run_mfma(x, z, logdet, gauss_loc, gauss_log_scale, logprob, ops, params
     ops: list of (kind, src_plane, gemm2_steps, offset); params packed by flow_pack._pack_mfma.
     ``D``: the kernel's row width when ``x`` is narrower (lean programs, tfk_flow_run_mfma_in): x (N, x_width) is read
     half by half into the heads of the two planes."""
-    global calls
     name = "tfk_flow_run_mfma"
     N, xw = _rows(x, name)
+    Dk, lead, trail = xw, (), ()          # the entry point's row width, its arguments behind x and behind the flag word
     if sum_out is not None:               # lean program + the fp64 sum of its log-probabilities (tfk_flow_run_mfma_sum)
         name = "tfk_flow_run_mfma_sum"
-        Dk = xw if D is None else D
-        ops_arr = _pack_ops(ops)
         if context is not None or logprob is None or sum_out.dtype != torch.float64 or sum_out.numel() != 1:
             raise NativeError(f"{name}: needs logprob, a 1-element float64 sum_out and no context")
-        for t, n in ((z, N * Dk), (logdet, N), (logprob, N), (gauss_loc, Dk), (gauss_log_scale, Dk)):
-            if t is not None and t.numel() != n:
-                raise NativeError(f"{name}: tensor with {t.numel()} elements, expected {n}")
-        ws = flow_sum_workspace(x)
-        args = (_f32(x, name), xw, _f32(z, name), _f32(logdet, name), _f32(gauss_loc, name),
-                _f32(gauss_log_scale, name), _f32(logprob, name), N, Dk, ops_arr, _n_ops(ops),
-                _f32(params, name), params.numel(),
-                (1 if accumulate else 0) | (2 if reverse_out else 0) | (4 if base_of_input else 0) | _stream_flag(),
-                ws.data_ptr(), sum_out.data_ptr())
-        with _device_guard(x):
-            rc = lib().tfk_flow_run_mfma_sum(*args, _stream(x))
-        calls += 1
-        _check(rc, name)
-        return
-    if context is not None:               # context-conditioned program (tfk_flow_run_mfma_ctx); rows at full width
+        Dk = xw if D is None else D
+        lead, trail = (xw,), (flow_sum_workspace(x).data_ptr(), sum_out.data_ptr())
+    elif context is not None:             # context-conditioned program (tfk_flow_run_mfma_ctx); rows at full width
         name = "tfk_flow_run_mfma_ctx"
-        Dk = xw
-        ops_arr = _pack_ops(ops)
         if context.dim() != 2 or context.shape[0] != N:
             raise NativeError(f"{name}: context must be (N, C), got {tuple(context.shape)}")
-        for t, n in ((z, N * Dk), (logdet, N), (logprob, N), (gauss_loc, Dk), (gauss_log_scale, Dk)):
-            if t is not None and t.numel() != n:
-                raise NativeError(f"{name}: tensor with {t.numel()} elements, expected {n}")
-        args = (_f32(x, name), _f32(context, name), int(context.shape[1]), _f32(z, name), _f32(logdet, name),
-                _f32(gauss_loc, name), _f32(gauss_log_scale, name), _f32(logprob, name), N, Dk, ops_arr, _n_ops(ops),
-                _f32(params, name), params.numel(),
-                (1 if accumulate else 0) | (2 if reverse_out else 0) | (4 if base_of_input else 0) | _stream_flag())
-        with _device_guard(x):
-            rc = lib().tfk_flow_run_mfma_ctx(*args, _stream(x))
-        calls += 1
-        _check(rc, name)
-        return
-    if D is not None and D != xw:
+        lead = (_f32(context, name), int(context.shape[1]))
+    elif D is not None and D != xw:
         name = "tfk_flow_run_mfma_in"
-        ops_arr = _pack_ops(ops)
-        for t, n in ((z, N * D), (logdet, N), (logprob, N), (gauss_loc, D), (gauss_log_scale, D)):
-            if t is not None and t.numel() != n:
-                raise NativeError(f"{name}: tensor with {t.numel()} elements, expected {n}")
-        args = (_f32(x, name), xw, _f32(z, name), _f32(logdet, name), _f32(gauss_loc, name),
-                _f32(gauss_log_scale, name), _f32(logprob, name), N, D, ops_arr, _n_ops(ops),
-                _f32(params, name), params.numel(),
-                (1 if accumulate else 0) | (2 if reverse_out else 0) | (4 if base_of_input else 0) | _stream_flag())
-        with _device_guard(x):
-            rc = lib().tfk_flow_run_mfma_in(*args, _stream(x))
-        calls += 1
-        _check(rc, name)
-        return
-    D = xw
+        Dk, lead = D, (xw,)
     ops_arr = _pack_ops(ops)
-    for t, n in ((z, N * D), (logdet, N), (logprob, N), (gauss_loc, D), (gauss_log_scale, D)):
-        if t is not None and t.numel() != n:
-            raise NativeError(f"{name}: tensor with {t.numel()} elements, expected {n}")
-    args = (_f32(x, name), _f32(z, name), _f32(logdet, name), _f32(gauss_loc, name),
-            _f32(gauss_log_scale, name), _f32(logprob, name), N, D, ops_arr, _n_ops(ops),
-            _f32(params, name), params.numel(),
-            (1 if accumulate else 0) | (2 if reverse_out else 0) | (4 if base_of_input else 0) | _stream_flag())
-    with _device_guard(x):
-        rc = lib().tfk_flow_run_mfma(*args, _stream(x))
-    calls += 1
-    _check(rc, name)
+    _flow_sizes(name, N, Dk, Dk, z, logdet, logprob, gauss_loc, gauss_log_scale)
+    _launch(name, x, _f32(x, name), *lead, _f32(z, name), _f32(logdet, name), _f32(gauss_loc, name),
+            _f32(gauss_log_scale, name), _f32(logprob, name), N, Dk, ops_arr, _n_ops(ops), _f32(params, name), params.numel(),
+            (1 if accumulate else 0) | (2 if reverse_out else 0) | (4 if base_of_input else 0) | _stream_flag(), *trail)
 
 
 def flow_run_wide(x, z, logdet, gauss_loc, gauss_log_scale, logprob, ops, params, accumulate=False,
@@ -1235,22 +1080,14 @@ def flow_run_wide(x, z, logdet, gauss_loc, gauss_log_scale, logprob, ops, params
     """Chain of affine / shift couplings on an even event size in (256, 2048] as one launch (tfk_flow_run_wide).
     x / z (N, D) at the logical width; ops and params packed by fused_wide.compile_wide; gauss_loc / gauss_log_scale in the
     kernel's column order (2 x the padded plane width).  z / logdet / logprob may be None."""
-    global calls
     name = "tfk_flow_run_wide"
     N, D = _rows(x, name)
     hp2 = 2 * ((D // 2 + 63) // 64 * 64)
     ops_arr = _pack_ops(ops)
-    for t, n in ((z, N * D), (logdet, N), (logprob, N), (gauss_loc, hp2), (gauss_log_scale, hp2)):
-        if t is not None and t.numel() != n:
-            raise NativeError(f"{name}: tensor with {t.numel()} elements, expected {n}")
-    args = (_f32(x, name), _f32(z, name), _f32(logdet, name), _f32(gauss_loc, name),
-            _f32(gauss_log_scale, name), _f32(logprob, name), N, D, ops_arr, _n_ops(ops),
-            _f32(params, name), params.numel(),
+    _flow_sizes(name, N, D, hp2, z, logdet, logprob, gauss_loc, gauss_log_scale)
+    _launch(name, x, _f32(x, name), _f32(z, name), _f32(logdet, name), _f32(gauss_loc, name), _f32(gauss_log_scale, name),
+            _f32(logprob, name), N, D, ops_arr, _n_ops(ops), _f32(params, name), params.numel(),
             (1 if accumulate else 0) | (2 if reverse_out else 0) | (4 if base_of_input else 0))
-    with _device_guard(x):
-        rc = lib().tfk_flow_run_wide(*args, _stream(x))
-    calls += 1
-    _check(rc, name)
 
 
 def glow_plan(layer: GlowLayer, D: int) -> dict:
@@ -1263,15 +1100,11 @@ def glow_plan(layer: GlowLayer, D: int) -> dict:
 
 def glow_coupling(rows: torch.Tensor, logdet: torch.Tensor, layer: GlowLayer, inverse: bool = False) -> None:
     """One convolutional coupling in place on the rows (conditioner, bounded output, transform, log-det added)."""
-    global calls
-    N, D = _rows(rows, "tfk_glow_coupling")
+    name = "tfk_glow_coupling"
+    N, D = _rows(rows, name)
     if logdet.numel() != N:
         raise NativeError(f"tfk_glow_coupling: logdet has {logdet.numel()} elements, expected {N}")
-    with _device_guard(rows):
-        rc = lib().tfk_glow_coupling(_f32(rows, "tfk_glow_coupling"), _f32(logdet, "tfk_glow_coupling"), N, D,
-                                     C.byref(layer), 1 if inverse else 0, _stream(rows))
-    calls += 1
-    _check(rc, "tfk_glow_coupling")
+    _launch(name, rows, _f32(rows, name), _f32(logdet, name), N, D, C.byref(layer), 1 if inverse else 0)
 
 
 def glow_level_pack(steps, D: int, D_level: int, samples: int = 0, block: int = 0) -> torch.Tensor:
@@ -1297,7 +1130,6 @@ def glow_level_info(blob_host: torch.Tensor) -> dict:
 def glow_level(rows_in: torch.Tensor, rows_out: torch.Tensor, logdet: torch.Tensor, row_idx: Optional[torch.Tensor],
                blob_host: torch.Tensor, blob_dev: torch.Tensor) -> None:
     """The couplings of one level back to back on rows held in the LDS (in place unless the level covers the whole row)."""
-    global calls
     name = "tfk_glow_level"
     N, D = _rows(rows_out, name)
     if rows_in.shape != rows_out.shape or logdet.numel() != N:
@@ -1306,58 +1138,40 @@ def glow_level(rows_in: torch.Tensor, rows_out: torch.Tensor, logdet: torch.Tens
         raise NativeError(f"{name}: row_idx must be an int32 tensor on the rows' device")
     if blob_host.device.type != "cpu" or blob_dev.device != rows_out.device:
         raise NativeError(f"{name}: the blob's two copies must live on the host and on the rows' device")
-    with _device_guard(rows_out):
-        rc = lib().tfk_glow_level(_f32(rows_in, name), _f32(rows_out, name), _f32(logdet, name), N, D,
-                                  None if row_idx is None else row_idx.data_ptr(), blob_host.data_ptr(),
-                                  blob_dev.data_ptr(), _stream(rows_out))
-    calls += 1
-    _check(rc, name)
+    _launch(name, rows_out, _f32(rows_in, name), _f32(rows_out, name), _f32(logdet, name), N, D,
+            None if row_idx is None else row_idx.data_ptr(), blob_host.data_ptr(), blob_dev.data_ptr())
 
 
 def rows_fma(rows: torch.Tensor, st: torch.Tensor) -> None:
     """rows[n, d] = st[d, 0] * rows[n, d] + st[d, 1] in place."""
-    global calls
-    N, D = _rows(rows, "tfk_rows_fma")
+    name = "tfk_rows_fma"
+    N, D = _rows(rows, name)
     if st.numel() != 2 * D:
         raise NativeError(f"tfk_rows_fma: st has {st.numel()} elements, expected 2 * {D}")
-    with _device_guard(rows):
-        rc = lib().tfk_rows_fma(_f32(rows, "tfk_rows_fma"), _f32(st, "tfk_rows_fma"), N, D, _stream(rows))
-    calls += 1
-    _check(rc, "tfk_rows_fma")
+    _launch(name, rows, _f32(rows, name), _f32(st, name), N, D)
 
 
 def rows_fma_gauss_logprob(rows, st, loc, log_scale, logdet_in, out) -> None:
     """out[n] = base log-density of st[d, 0] * rows[n, d] + st[d, 1] (+ logdet_in[n]); the rows are only read."""
-    global calls
     name = "tfk_rows_fma_gauss_logprob"
     N, D = _rows(rows, name)
     if st.numel() != 2 * D or loc.numel() != D or log_scale.numel() != D or out.numel() != N:
         raise NativeError(f"{name}: bad parameter / out shape")
-    with _device_guard(rows):
-        rc = lib().tfk_rows_fma_gauss_logprob(_f32(rows, name), _f32(st, name), _f32(loc, name), _f32(log_scale, name),
-                                              _f32(logdet_in, name), _f32(out, name), N, D, _stream(rows))
-    calls += 1
-    _check(rc, name)
+    _launch(name, rows, _f32(rows, name), _f32(st, name), _f32(loc, name), _f32(log_scale, name), _f32(logdet_in, name),
+            _f32(out, name), N, D)
 
 
 def sum_f32(values: torch.Tensor) -> torch.Tensor:
     """fp64 sum of an fp32 vector as a 1-element float64 device tensor (feeds the all-reduce)."""
-    global calls
     v = values.reshape(-1)
     N = v.numel()
     _f32(v, "tfk_sum_f32")
     out = torch.empty(1, dtype=torch.float64, device=v.device)
     if N < (1 << 14):                 # one workgroup, no workspace (SURVEY 8(b)'s four-argument form)
-        with _device_guard(v):
-            rc = lib().tfk_sum_f32(_f32(v, "tfk_sum_f32"), out.data_ptr(), N, _stream(v))
-        calls += 1
-        _check(rc, "tfk_sum_f32")
-        return out
-    ws = torch.empty(int(lib().tfk_sum_workspace_bytes(N)), dtype=torch.uint8, device=v.device)
-    with _device_guard(v):
-        rc = lib().tfk_sum_f32_ws(_f32(v, "tfk_sum_f32_ws"), out.data_ptr(), ws.data_ptr(), N, _stream(v))
-    calls += 1
-    _check(rc, "tfk_sum_f32_ws")
+        _launch("tfk_sum_f32", v, v.data_ptr(), out.data_ptr(), N)
+    else:
+        ws = torch.empty(int(lib().tfk_sum_workspace_bytes(N)), dtype=torch.uint8, device=v.device)
+        _launch("tfk_sum_f32_ws", v, v.data_ptr(), out.data_ptr(), ws.data_ptr(), N)
     return out
 
 
