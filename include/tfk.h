@@ -599,23 +599,32 @@ int tfk_convnet_train_linear_wgrad(const float *g, const float *a16, const float
  *            image -- in KERNEL ORDER.  1x1 convolution: ceil(n_params / 16) tiles, rows in the order of h.  Affine:
  *            2 * ceil(T / 16) tiles; for the target listed at position 16 m + j of tgt_idx, row 32 m + j is its scale
  *            logit (h[n, t, 0]) and row 32 m + 16 + j its shift (h[n, t, 1]); rows of padding are zero.  Shift:
- *            ceil(T / 16) tiles, row 16 m + j = the shift of the target at position 16 m + j of tgt_idx
+ *            ceil(T / 16) tiles, row 16 m + j = the shift of the target at position 16 m + j of tgt_idx.  Deep sigmoidal
+ *            (kind 3, P = 3 * hidden_dim * n_components parameters per target, h[n, t, p] in the order of tfk_dsf_coupling_*):
+ *            P * ceil(T / 16) tiles, row (m P + p) 16 + j = parameter p of the target at position 16 m + j of tgt_idx
  *   b_eff    16 * tiles floats in the same row order: log2(e) times (Linear bias + its 84 frame columns times the second
  *            ConvModifier's bias) -- the kernel's sigmoid is 1 / (1 + exp2(-h log2 e))
- * tgt_idx (affine, shift) may list the targets in any order -- ascending physical position makes the 16 targets of a tile pair
+ * Kind 3 runs in workgroups of at most 256 threads (block = 0 or <= 256), forward and inverse (the reference's bisection
+ * per element, as tfk_dsf_coupling_inv); tfk_glow_level does not take it.  The kind adds no field and TFK_ABI_VERSION stays
+ * 29, so the version does not tell whether a library has it: probe with tfk_glow_plan on a layer of kind = 3 (no device
+ * needed), which a library without the kind answers with TFK_EINVAL.
+ * tgt_idx (affine, shift, deep sigmoidal) may list the targets in any order -- ascending physical position makes the 16 targets of a tile pair
  * neighbours in the row -- padded, like tgt_st, to a multiple of 16 entries.
  * Supported: first ConvModifier as the reference builds it for images up to 32 pixels (classic.py:21-33: kernel 1 and padding
  * (32 - size) / 2 along an axis where 32 - size is even, kernel 2 and padding (33 - size) / 2 where it is odd -- e.g. the
  * 7-row conditioner images of 28x28 inputs), ConvNet kernels (8, 8, 4), 1x1 convolutions of <= 16 channels.
  * slots / block / cg1 / cg2 / grid = 0 let the library choose the launch shape (tfk_glow_plan reports it). */
 typedef struct tfk_glow_layer {
-    int32_t kind;              /* 0 affine, 1 invertible 1x1 convolution, 2 shift (z = x +/- h, log-det 0; affine.py:137-159) */
+    int32_t kind;              /* 0 affine, 1 invertible 1x1 convolution, 2 shift (z = x +/- h, log-det 0; affine.py:137-159),
+                                * 3 deep sigmoidal (Sigmoid / DeepSigmoid, transformers/combination/sigmoid.py) */
     int32_t c_in, hi, wi;      /* conditioner input image */
     int32_t oy, ox;            /* where the modifier's non-constant rectangle starts in its 32x32 frame: padding - (kernel - 1) */
     int32_t kh, kw;            /* first ConvModifier's kernel, 1 or 2 per axis (0 = 1); the rectangle is (hi + kh - 1, wi + kw - 1) */
     int32_t T;                 /* target elements */
-    int32_t n_params;          /* 2 T (affine), T (shift) or n + n (n - 1) (1x1 convolution of n channels) */
-    int32_t n_ch, hw;          /* 1x1 convolution: target channels, pixels per channel (T = n_ch * hw); else 0 */
+    int32_t n_params;          /* 2 T (affine), T (shift), n + n (n - 1) (1x1 convolution of n channels) or
+                                * T * 3 * hidden_dim * n_components (deep sigmoidal) */
+    int32_t n_ch, hw;          /* 1x1 convolution: target channels, pixels per channel (T = n_ch * hw); deep sigmoidal:
+                                * n_ch = n_components, hw = hidden_dim (a size tfk_dsf_supported accepts); else 0 */
     int32_t slots, block, cg1, cg2, grid;   /* launch shape overrides, 0 = default */
     const int32_t *src_idx;    /* device int32[c_in * hi * wi] */
     const float *src_st;       /* device float[2 * c_in * hi * wi] */

@@ -11,5 +11,7 @@ from torchflows_amd.bijections.finite.autoregressive.architectures import (  # n
     RealNVP, CouplingRQNSF, CouplingLRS, NICE, MAF, IAF, MaskedAutoregressiveRQNSF,
     InverseAutoregressiveRQNSF, MaskedAutoregressiveLRS, InverseAutoregressiveLRS, CouplingDeepSF,
     MaskedAutoregressiveDeepSF, InverseAutoregressiveDeepSF)
+from torchflows_amd.bijections.finite.multiscale.architectures import (  # noqa: F401
+    MultiscaleDeepSigmoid, DeepSigmoidGlow)
 
 __version__ = "0.1.0"

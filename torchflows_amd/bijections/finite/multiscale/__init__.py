@@ -1,5 +1,5 @@
 from torchflows_amd.bijections.finite.multiscale.architectures import (  # noqa: F401
-    AffineGlow, MultiscaleNICE, MultiscaleRealNVP, ShiftGlow)
+    AffineGlow, DeepSigmoidGlow, MultiscaleDeepSigmoid, MultiscaleNICE, MultiscaleRealNVP, ShiftGlow)
 from torchflows_amd.bijections.finite.multiscale.base import (  # noqa: F401
     CheckerboardCoupling, ChannelWiseCoupling, GlowChannelWiseCoupling, GlowCheckerboardCoupling,
     Invertible1x1ConvolutionalCoupling, MultiscaleBijection, NormalizedChannelWiseCoupling,

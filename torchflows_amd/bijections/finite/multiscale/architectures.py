@@ -1,8 +1,9 @@
 """Multiscale presets on the hot path (reference ``multiscale/architectures.py``: shape
 checks :18-44, ``MultiscaleRealNVP`` :47-68, ``MultiscaleNICE`` :71-92, ``AffineGlow``
-:198-212, ``ShiftGlow`` :215-229)."""
+:198-212, ``ShiftGlow`` :215-229, ``MultiscaleDeepSigmoid`` :136-148, ``DeepSigmoidGlow`` :266-280)."""
 from __future__ import annotations
 
+from torchflows_amd.bijections.finite.autoregressive.transformers.combination.sigmoid import DeepSigmoid
 from torchflows_amd.bijections.finite.autoregressive.transformers.linear.affine import Affine, Shift
 from torchflows_amd.bijections.finite.multiscale.base import (
     GlowChannelWiseCoupling, GlowCheckerboardCoupling, MultiscaleBijection)
@@ -54,6 +55,20 @@ class AffineGlow(MultiscaleBijection):
     def __init__(self, event_shape, n_layers: int = None, **kwargs):
         event_shape, n_layers = _resolve(event_shape, n_layers)
         super().__init__(event_shape=event_shape, transformer_class=Affine,
+                         checkerboard_class=GlowCheckerboardCoupling,
+                         channel_wise_class=GlowChannelWiseCoupling, n_blocks=n_layers, **kwargs)
+
+
+class MultiscaleDeepSigmoid(MultiscaleBijection):
+    def __init__(self, event_shape, n_layers: int = None, **kwargs):
+        event_shape, n_layers = _resolve(event_shape, n_layers)
+        super().__init__(event_shape=event_shape, transformer_class=DeepSigmoid, n_blocks=n_layers, **kwargs)
+
+
+class DeepSigmoidGlow(MultiscaleBijection):
+    def __init__(self, event_shape, n_layers: int = None, **kwargs):
+        event_shape, n_layers = _resolve(event_shape, n_layers)
+        super().__init__(event_shape=event_shape, transformer_class=DeepSigmoid,
                          checkerboard_class=GlowCheckerboardCoupling,
                          channel_wise_class=GlowChannelWiseCoupling, n_blocks=n_layers, **kwargs)
 

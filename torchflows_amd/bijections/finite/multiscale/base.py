@@ -185,7 +185,9 @@ class MultiscaleBijection(Bijection):
             return None     # (training mode: BatchNorm takes batch statistics, nothing to fold -- and no compile attempt per step)
         from torchflows_amd import image_program
         prog = image_program.get_program(self, d, x.device)
-        return None if prog is None else image_program.run(prog, x, self.event_shape)
+        if prog is None or not image_program.fills_device(prog, x.numel() // prog.D, d, x.device):
+            return None     # (not covered, or a batch too small for the deep sigmoidal launches: layer by layer)
+        return image_program.run(prog, x, self.event_shape)
 
     @forward_method
     def forward(self, x: torch.Tensor, context: torch.Tensor = None) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -31,7 +31,7 @@ struct GlowGeom {
     int fixed_floats;                   // LDS floats in front of the slots
     int slots, tile_rows;               // G, NS
     int T, n_params, n_tiles, D;
-    int kind, n_ch, hw;                 // 1x1 convolution: channels, pixels
+    int kind, n_ch, hw;                 // 1x1 convolution: channels, pixels; deep sigmoidal: components C, hidden_dim K
     int cg1, cg2;                       // output channels per lane task in conv block 1 / 2
     int h_stride;                       // kind 1: floats per sample in the parameter buffer
     int skip;                           // timing ablations only (TFK_GLOW_SKIP): 1 no S0, 2 no conv blocks, 4 no Linear / transform
@@ -128,6 +128,147 @@ __device__ __forceinline__ void conv_stage_cg(int cg, float *slot0, int slot_flo
     else conv_stage<CI, CO, 2, AFFINE>(slot0, slot_floats, in_off, ih, iw, out_off, oh, ow, oy0, ox0, ph, pw, G, w, bias, sc, sh);
 }
 
+// ---- the stages every coupling kernel starts with (tfk_glow.hip, tfk_glow_dsf.hip): from the rows to the 16 numbers per
+// sample that feed the Linear layer ------------------------------------------------------------------------------
+
+// S0: the source elements of G resident samples (gathered through the layer's table, pending maps applied)
+// through the first ConvModifier into the modifier buffer's rectangle.  ONE: the 1x1 kernel (every BASELINE shape), taps and
+// bounds tests compiled out (the general form costs the 1x1 case 5 %, same-box A/B).
+template <bool ONE>
+__device__ __forceinline__ void s0_modifier(const GlowGeom &g, const float *rows, long long N, long long row_first, int G,
+                                            float *slot0, const int *__restrict__ src_idx,
+                                            const float2 *__restrict__ src_st, const float *__restrict__ wts)
+{
+    const int npix = g.hi * g.wi, rpix = g.rh * g.rw;
+    const float *bm = wts + gw_bm(g.cm);
+    const int taps = ONE ? 1 : g.kh * g.kw;
+    for (int t = threadIdx.x; t < G * rpix; t += blockDim.x) {
+        const int slot = t / rpix, pix = t - slot * rpix;
+        const int iy = pix / g.rw, ix = pix - iy * g.rw;
+        long long row = row_first + slot;
+        if (row > N - 1) row = N - 1;
+        const float *xr = rows + row * g.D;
+        float o0 = bm[0], o1 = bm[1], o2 = bm[2], o3 = bm[3];
+        for (int tap = 0; tap < taps; ++tap) {
+            bool inside = true;
+            int spix = pix;
+            if (!ONE) {
+                const int ky = tap / g.kw, kx = tap - ky * g.kw;
+                const int sy = iy - (g.kh - 1) + ky, sx = ix - (g.kw - 1) + kx;      // out[Y] = sum_k W[k] x[Y + k - pad]
+                inside = sy >= 0 && sy < g.hi && sx >= 0 && sx < g.wi;
+                spix = inside ? sy * g.wi + sx : 0;
+            }
+            for (int c0 = 0; c0 < g.c_in; c0 += 4) {             // four channels' loads in flight together
+                int idx[4];
+                float2 st[4];
+                float raw[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int c = c0 + u < g.c_in ? c0 + u : g.c_in - 1;
+                    const int e = c * npix + spix;
+                    idx[u] = src_idx[e];
+                    st[u] = src_st[e];
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) raw[u] = xr[idx[u]];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int c = c0 + u;
+                    const bool on = c < g.c_in;
+                    const int w = (on ? c : 0) * taps + tap;
+                    const float v = (on && inside) ? fmaf(st[u].x, raw[u], st[u].y) : 0.0f;
+                    o0 = fmaf(wts[w], v, o0);
+                    o1 = fmaf(wts[g.cm + w], v, o1);
+                    o2 = fmaf(wts[2 * g.cm + w], v, o2);
+                    o3 = fmaf(wts[3 * g.cm + w], v, o3);
+                }
+            }
+        }
+        float *a = slot0 + slot * g.slot_floats + (g.oy + iy - g.a0y0) * g.a0w + (g.ox + ix - g.a0x0);
+        const int plane = g.a0h * g.a0w;
+        a[0] = o0, a[plane] = o1, a[2 * plane] = o2, a[3 * plane] = o3;
+    }
+}
+
+// Once per workgroup: everything of the slots' buffers that no sample changes (zero outside the frames, the first
+// modifier's bias, bg1, bg2); ends with a barrier.
+__device__ __forceinline__ void glow_background(const GlowGeom &g, float *slot0, const float *__restrict__ wts,
+                                                const float *__restrict__ bg1, const float *__restrict__ bg2)
+{
+    const int tid = threadIdx.x, nthr = blockDim.x, G = g.slots;
+    const float *bm = wts + gw_bm(g.cm);
+    const int a0 = 4 * g.a0h * g.a0w, b1 = 8 * g.b1h * g.b1w;
+    for (int i = tid; i < G * a0; i += nthr) {
+        const int slot = i / a0, e = i - slot * a0;
+        const int ch = e / (g.a0h * g.a0w), r = (e / g.a0w) % g.a0h, c = e % g.a0w;
+        const int y = g.a0y0 + r, x = g.a0x0 + c;
+        const bool in = y >= 0 && y < kGlowFrame && x >= 0 && x < kGlowFrame;
+        slot0[slot * g.slot_floats + e] = in ? bm[ch] : 0.0f;
+    }
+    for (int i = tid; i < G * b1; i += nthr) {
+        const int slot = i / b1, e = i - slot * b1;
+        const int ch = e / (g.b1h * g.b1w), r = (e / g.b1w) % g.b1h, c = e % g.b1w;
+        const int y = g.b1y0 + r, x = g.b1x0 + c;
+        const bool in = y >= 0 && y < 16 && x >= 0 && x < 16;
+        slot0[slot * g.slot_floats + g.off_p1 + e] = in ? bg1[(ch * 16 + y) * 16 + x] : 0.0f;
+    }
+    for (int i = tid; i < G * 800; i += nthr) {
+        const int slot = i / 800, e = i - slot * 800;
+        const int ch = e / 100, r = (e / 10) % 10, c = e % 10;
+        const int y = r - 1, x = c - 1;
+        const bool in = y >= 0 && y < 8 && x >= 0 && x < 8;
+        slot0[slot * g.slot_floats + g.off_p2 + e] = in ? bg2[(ch * 8 + y) * 8 + x] : 0.0f;
+    }
+    __syncthreads();
+}
+
+// S0 .. S4 for the tile of g.tile_rows samples that starts at row_base, g.slots of them per round: V[sample][16] holds
+// what the Linear layer reads (rows past N - 1 repeat the last one); ends with a barrier.
+__device__ __forceinline__ void glow_conditioner16(const GlowGeom &g, const float *rows, long long N, long long row_base,
+                                                   float *slot0, float *V, const int *__restrict__ src_idx,
+                                                   const float2 *__restrict__ src_st, const float *__restrict__ wts)
+{
+    const int tid = threadIdx.x, nthr = blockDim.x, G = g.slots;
+    for (int s0 = 0; s0 < g.tile_rows; s0 += G) {
+        // ---- S0: pending map + ConvModifier (c_in -> 4 channels; kernel 1x1, or 2 wide along an axis whose padding is
+        //      odd, classic.py:26-33) into the rectangle of the frame that is not the bias ----
+        if (!(g.skip & 1)) {
+            if (g.kh * g.kw == 1) s0_modifier<true>(g, rows, N, row_base + s0, G, slot0, src_idx, src_st, wts);
+            else s0_modifier<false>(g, rows, N, row_base + s0, G, slot0, src_idx, src_st, wts);
+        }
+        __syncthreads();
+        // ---- S1 .. S3: the three conv blocks on their windows ----
+        const int ci = g.cm;
+        if (!(g.skip & 2)) {
+            conv_stage_cg<4, 8, true>(g.cg1, slot0, g.slot_floats, 0, g.a0h, g.a0w, g.off_p1, g.b1h, g.b1w,
+                                      g.p1y0 - g.b1y0, g.p1x0 - g.b1x0, g.p1h, g.p1w, G, wts + gw_w1(ci),
+                                      wts + gw_b1(ci), wts + gw_b1(ci) + 8, wts + gw_b1(ci) + 16);
+            __syncthreads();
+            conv_stage_cg<8, 8, true>(g.cg2, slot0, g.slot_floats, g.off_p1, g.b1h, g.b1w, g.off_p2, 10, 10,
+                                      g.p2y0 + 1, g.p2x0 + 1, g.p2h, g.p2w, G, wts + gw_w2(ci), wts + gw_b2(ci),
+                                      wts + gw_b2(ci) + 8, wts + gw_b2(ci) + 16);
+            __syncthreads();
+            conv_stage<8, 4, 2, false>(slot0, g.slot_floats, g.off_p2, 10, 10, g.off_p3, 4, 4, 0, 0, 4, 4, G,
+                                       wts + gw_w3(ci), wts + gw_b3(ci), nullptr, nullptr);
+            __syncthreads();
+        }
+        // ---- S4: BatchNorm 3 + second ConvModifier (4 -> 1 channel), folded on the host ----
+        for (int t = tid; t < G * 16; t += nthr) {
+            const int slot = t >> 4, p = t & 15;
+            const float *p3 = slot0 + slot * g.slot_floats + g.off_p3 + p;
+            const float *m2 = wts + gw_m2(ci);
+            float v = m2[4];
+            v = fmaf(m2[0], p3[0], v);
+            v = fmaf(m2[1], p3[16], v);
+            v = fmaf(m2[2], p3[32], v);
+            v = fmaf(m2[3], p3[48], v);
+            V[(s0 + slot) * 16 + p] = v;
+        }
+        // (the next round's S0 writes A0, last read before two barriers; P3 is rewritten after three more)
+    }
+    __syncthreads();
+}
+
 // lo + (hi - lo) * sigmoid(h) with (lo, hi) = (-2, 2); the caller hands in h * log2(e) (the rows of W_eff / b_eff arrive
 // pre-multiplied), so the exponential is one v_exp_f32; s * 4 is exact, so the reference's multiply-then-add is one fma
 __device__ __forceinline__ float bounded4(float h_log2e)
@@ -164,5 +305,9 @@ constexpr int kGlowLdsBytes = 160 * 1024;
 
 // validated geometry of one layer (no launch shape): shared by tfk_glow_plan / tfk_glow_coupling / the level packer
 int glow_geometry_base(const tfk_glow_layer *L, int32_t D, GlowGeom &g, const char *fn);
+
+// kind 3 (deep sigmoidal, tfk_glow_dsf.hip) behind tfk_glow_coupling: g, block and lds as tfk_glow_plan reports them
+int glow_dsf_launch(float *rows, float *logdet, int64_t N, const GlowGeom &g, int block, size_t lds,
+                    const tfk_glow_layer *layer, int inverse, hipStream_t s, const char *fn);
 
 }  // namespace tfk

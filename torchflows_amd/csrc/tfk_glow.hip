@@ -36,65 +36,6 @@
 
 namespace tfk {
 
-// S0 of k_glow_coupling: the source elements of G resident samples (gathered through the layer's table, pending maps applied)
-// through the first ConvModifier into the modifier buffer's rectangle.  ONE: the 1x1 kernel (every BASELINE shape), taps and
-// bounds tests compiled out (the general form costs the 1x1 case 5 %, same-box A/B).
-template <bool ONE>
-__device__ __forceinline__ void s0_modifier(const GlowGeom &g, const float *rows, long long N, long long row_first, int G,
-                                            float *slot0, const int *__restrict__ src_idx,
-                                            const float2 *__restrict__ src_st, const float *__restrict__ wts)
-{
-    const int npix = g.hi * g.wi, rpix = g.rh * g.rw;
-    const float *bm = wts + gw_bm(g.cm);
-    const int taps = ONE ? 1 : g.kh * g.kw;
-    for (int t = threadIdx.x; t < G * rpix; t += blockDim.x) {
-        const int slot = t / rpix, pix = t - slot * rpix;
-        const int iy = pix / g.rw, ix = pix - iy * g.rw;
-        long long row = row_first + slot;
-        if (row > N - 1) row = N - 1;
-        const float *xr = rows + row * g.D;
-        float o0 = bm[0], o1 = bm[1], o2 = bm[2], o3 = bm[3];
-        for (int tap = 0; tap < taps; ++tap) {
-            bool inside = true;
-            int spix = pix;
-            if (!ONE) {
-                const int ky = tap / g.kw, kx = tap - ky * g.kw;
-                const int sy = iy - (g.kh - 1) + ky, sx = ix - (g.kw - 1) + kx;      // out[Y] = sum_k W[k] x[Y + k - pad]
-                inside = sy >= 0 && sy < g.hi && sx >= 0 && sx < g.wi;
-                spix = inside ? sy * g.wi + sx : 0;
-            }
-            for (int c0 = 0; c0 < g.c_in; c0 += 4) {             // four channels' loads in flight together
-                int idx[4];
-                float2 st[4];
-                float raw[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int c = c0 + u < g.c_in ? c0 + u : g.c_in - 1;
-                    const int e = c * npix + spix;
-                    idx[u] = src_idx[e];
-                    st[u] = src_st[e];
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) raw[u] = xr[idx[u]];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int c = c0 + u;
-                    const bool on = c < g.c_in;
-                    const int w = (on ? c : 0) * taps + tap;
-                    const float v = (on && inside) ? fmaf(st[u].x, raw[u], st[u].y) : 0.0f;
-                    o0 = fmaf(wts[w], v, o0);
-                    o1 = fmaf(wts[g.cm + w], v, o1);
-                    o2 = fmaf(wts[2 * g.cm + w], v, o2);
-                    o3 = fmaf(wts[3 * g.cm + w], v, o3);
-                }
-            }
-        }
-        float *a = slot0 + slot * g.slot_floats + (g.oy + iy - g.a0y0) * g.a0w + (g.ox + ix - g.a0x0);
-        const int plane = g.a0h * g.a0w;
-        a[0] = o0, a[plane] = o1, a[2 * plane] = o2, a[3 * plane] = o3;
-    }
-}
-
 template <int KIND, bool INV>
 __global__ __launch_bounds__(1024) void k_glow_coupling(float *rows, float *logdet, long long N, GlowGeom g,
                                                         const int *__restrict__ src_idx,
@@ -113,80 +54,16 @@ __global__ __launch_bounds__(1024) void k_glow_coupling(float *rows, float *logd
     float *slot0 = lds + g.fixed_floats;
     const int tid = threadIdx.x, nthr = blockDim.x;
     const int lane = tid & 63, wave = tid >> 6, nw = nthr >> 6;
-    const int G = g.slots;
     const int D = g.D;
-    const float *bm = wts + gw_bm(g.cm);
 
-    // ---- once per workgroup: everything of the buffers that no sample changes ----
-    {
-        const int a0 = 4 * g.a0h * g.a0w, b1 = 8 * g.b1h * g.b1w;
-        for (int i = tid; i < G * a0; i += nthr) {
-            const int slot = i / a0, e = i - slot * a0;
-            const int ch = e / (g.a0h * g.a0w), r = (e / g.a0w) % g.a0h, c = e % g.a0w;
-            const int y = g.a0y0 + r, x = g.a0x0 + c;
-            const bool in = y >= 0 && y < kGlowFrame && x >= 0 && x < kGlowFrame;
-            slot0[slot * g.slot_floats + e] = in ? bm[ch] : 0.0f;
-        }
-        for (int i = tid; i < G * b1; i += nthr) {
-            const int slot = i / b1, e = i - slot * b1;
-            const int ch = e / (g.b1h * g.b1w), r = (e / g.b1w) % g.b1h, c = e % g.b1w;
-            const int y = g.b1y0 + r, x = g.b1x0 + c;
-            const bool in = y >= 0 && y < 16 && x >= 0 && x < 16;
-            slot0[slot * g.slot_floats + g.off_p1 + e] = in ? bg1[(ch * 16 + y) * 16 + x] : 0.0f;
-        }
-        for (int i = tid; i < G * 800; i += nthr) {
-            const int slot = i / 800, e = i - slot * 800;
-            const int ch = e / 100, r = (e / 10) % 10, c = e % 10;
-            const int y = r - 1, x = c - 1;
-            const bool in = y >= 0 && y < 8 && x >= 0 && x < 8;
-            slot0[slot * g.slot_floats + g.off_p2 + e] = in ? bg2[(ch * 8 + y) * 8 + x] : 0.0f;
-        }
-    }
-    __syncthreads();
+    glow_background(g, slot0, wts, bg1, bg2);
 
     const long long n_tiles_rows = (N + g.tile_rows - 1) / g.tile_rows;
     for (long long tile = blockIdx.x; tile < n_tiles_rows; tile += gridDim.x) {
         const long long row_base = tile * g.tile_rows;
         const int nrows = (int)((N - row_base) < (long long)g.tile_rows ? (N - row_base) : (long long)g.tile_rows);
 
-        for (int s0 = 0; s0 < g.tile_rows; s0 += G) {
-            // ---- S0: pending map + ConvModifier (c_in -> 4 channels; kernel 1x1, or 2 wide along an axis whose padding is
-            //      odd, classic.py:26-33) into the rectangle of the frame that is not the bias ----
-            if (!(g.skip & 1)) {
-                if (g.kh * g.kw == 1) s0_modifier<true>(g, rows, N, row_base + s0, G, slot0, src_idx, src_st, wts);
-                else s0_modifier<false>(g, rows, N, row_base + s0, G, slot0, src_idx, src_st, wts);
-            }
-            __syncthreads();
-            // ---- S1 .. S3: the three conv blocks on their windows ----
-            const int ci = g.cm;
-            if (!(g.skip & 2)) {
-            conv_stage_cg<4, 8, true>(g.cg1, slot0, g.slot_floats, 0, g.a0h, g.a0w, g.off_p1, g.b1h, g.b1w,
-                                      g.p1y0 - g.b1y0, g.p1x0 - g.b1x0, g.p1h, g.p1w, G, wts + gw_w1(ci),
-                                      wts + gw_b1(ci), wts + gw_b1(ci) + 8, wts + gw_b1(ci) + 16);
-            __syncthreads();
-            conv_stage_cg<8, 8, true>(g.cg2, slot0, g.slot_floats, g.off_p1, g.b1h, g.b1w, g.off_p2, 10, 10,
-                                      g.p2y0 + 1, g.p2x0 + 1, g.p2h, g.p2w, G, wts + gw_w2(ci), wts + gw_b2(ci),
-                                      wts + gw_b2(ci) + 8, wts + gw_b2(ci) + 16);
-            __syncthreads();
-            conv_stage<8, 4, 2, false>(slot0, g.slot_floats, g.off_p2, 10, 10, g.off_p3, 4, 4, 0, 0, 4, 4, G,
-                                       wts + gw_w3(ci), wts + gw_b3(ci), nullptr, nullptr);
-            __syncthreads();
-            }
-            // ---- S4: BatchNorm 3 + second ConvModifier (4 -> 1 channel), folded on the host ----
-            for (int t = tid; t < G * 16; t += nthr) {
-                const int slot = t >> 4, p = t & 15;
-                const float *p3 = slot0 + slot * g.slot_floats + g.off_p3 + p;
-                const float *m2 = wts + gw_m2(ci);
-                float v = m2[4];
-                v = fmaf(m2[0], p3[0], v);
-                v = fmaf(m2[1], p3[16], v);
-                v = fmaf(m2[2], p3[32], v);
-                v = fmaf(m2[3], p3[48], v);
-                V[(s0 + slot) * 16 + p] = v;
-            }
-            // (the next round's S0 writes A0, last read before two barriers; P3 is rewritten after three more)
-        }
-        __syncthreads();
+        glow_conditioner16(g, rows, N, row_base, slot0, V, src_idx, src_st, wts);
 
         // ---- Linear layer on the matrix cores + bounded output + transform ----
         const int j = lane & 15, q = lane >> 4;
@@ -441,7 +318,8 @@ namespace tfk {
 int glow_geometry_base(const tfk_glow_layer *L, int32_t D, GlowGeom &g, const char *fn)
 {
     if (!L) return fail(TFK_EINVAL, "%s: null layer", fn);
-    if (L->kind < 0 || L->kind > 2) return fail(TFK_EINVAL, "%s: kind %d (0 affine, 1 invertible 1x1 convolution, 2 shift)", fn, L->kind);
+    if (L->kind < 0 || L->kind > 3)
+        return fail(TFK_EINVAL, "%s: kind %d (0 affine, 1 invertible 1x1 convolution, 2 shift, 3 deep sigmoidal)", fn, L->kind);
     const int kh = L->kh > 0 ? L->kh : 1, kw = L->kw > 0 ? L->kw : 1;
     if (kh > 2 || kw > 2) return fail(TFK_EINVAL, "%s: modifier kernel %dx%d (1 or 2 per axis)", fn, kh, kw);
     if (L->c_in < 1 || L->hi < 1 || L->wi < 1 || L->oy < 0 || L->ox < 0 || L->oy + L->hi + kh - 1 > kGlowFrame ||
@@ -458,11 +336,16 @@ int glow_geometry_base(const tfk_glow_layer *L, int32_t D, GlowGeom &g, const ch
         return fail(TFK_EINVAL, "%s: 1x1 convolution with %d channels x %d pixels (T = %d, n_params = %d): need "
                     "1 <= channels <= %d, T = channels * pixels, n_params = n + n (n - 1)", fn, L->n_ch, L->hw, L->T,
                     L->n_params, kGlowMaxCh);
+    if (L->kind == 3 && (!tfk_dsf_supported(L->n_ch, L->hw) || (int64_t)L->n_params != (int64_t)L->T * 3 * L->hw * L->n_ch))
+        return fail(TFK_EINVAL, "%s: deep sigmoidal coupling of %d targets with %d components of hidden_dim %d, n_params = %d: "
+                    "need a size tfk_dsf_supported accepts and n_params = T * 3 * hidden_dim * n_components", fn, L->T, L->n_ch,
+                    L->hw, L->n_params);
     g = GlowGeom{};
     g.c_in = L->c_in, g.hi = L->hi, g.wi = L->wi, g.oy = L->oy, g.ox = L->ox;
     g.kh = kh, g.kw = kw, g.rh = L->hi + kh - 1, g.rw = L->wi + kw - 1, g.cm = L->c_in * kh * kw;
     g.T = L->T, g.n_params = L->n_params, g.D = D;
     g.n_tiles = L->kind == 0 ? 2 * ((L->T + 15) / 16) : (L->n_params + 15) / 16;        // (shift: one tile per 16 targets)
+    if (L->kind == 3) g.n_tiles = 3 * L->hw * L->n_ch * ((L->T + 15) / 16);             // (3 K C tiles per 16 targets)
     g.kind = L->kind, g.n_ch = L->n_ch, g.hw = L->hw;
     g.h_stride = g.n_tiles * 16 + 1;
     g.fixed_floats = 512 + (L->kind == 1 ? ((kGlowMaxRows * g.h_stride + 3) & ~3) : 0);
@@ -485,6 +368,8 @@ int glow_geometry(const tfk_glow_layer *L, int32_t D, GlowGeom &g, int *block, c
     if (!glow_plan(g, L->slots, L->block, L->cg1, L->cg2, block))
         return fail(TFK_EINVAL, "%s: no launch shape fits (slots %d, block %d, channel groups %d / %d; %d B per slot)",
                     fn, L->slots, L->block, L->cg1, L->cg2, 4 * g.slot_floats);
+    if (L->kind == 3 && *block > 256)
+        return fail(TFK_EINVAL, "%s: a deep sigmoidal coupling runs in workgroups of at most 256 threads, got %d", fn, *block);
     return TFK_OK;
 }
 
@@ -547,6 +432,8 @@ int tfk_glow_coupling(float *rows, float *logdet, int64_t N, int32_t D, const tf
                            reinterpret_cast<const float4 *>(layer->w_eff),                                           \
                            reinterpret_cast<const float4 *>(layer->b_eff));                                          \
     } while (0)
+    if (layer->kind == 3)                  // (tfk_glow_dsf.hip: its own kernels, grid from their occupancy)
+        return glow_dsf_launch(rows, logdet, N, g, block, lds, layer, inverse, s, fn);
     if (layer->kind == 0 && !inverse) TFK_GLOW(0, false);
     else if (layer->kind == 0) TFK_GLOW(0, true);
     else if (layer->kind == 2 && !inverse) TFK_GLOW(2, false);

@@ -742,7 +742,7 @@ class Flow(BaseFlow):
             return None
         d = method_direction(b.forward)
         prog = None if d is None else image_program.get_program(b, d, x.device)
-        if prog is None:
+        if prog is None or not image_program.fills_device(prog, x.numel() // prog.D, d, x.device):
             return None
         return image_program.log_prob(prog, x, self.event_shape, self.base.loc.detach(), self.base.log_scale.detach())
 

@@ -19,7 +19,7 @@ recursion is *compiled* once per parameter version into a flat list of ``tfk_glo
   ``(n_params, 16)`` matrix in MFMA tile order.
 
 A model the compiler does not cover (another conditioner, a modifier that is a real convolution -- images larger than 32
-pixels --, a transformer other than Affine / Shift / the 1x1 convolution, a context, ``invert()``-ed layers, an
+pixels --, a transformer other than Affine / Shift / the 1x1 convolution / Sigmoid and DeepSigmoid, a context, ``invert()``-ed layers, an
 ActNorm that still waits for its first batch) returns None and runs layer by layer as before.
 """
 from __future__ import annotations
@@ -197,6 +197,13 @@ def layer_cost(layer) -> dict:
     if layer.kind == 1:
         macs += layer.hw * layer.n_ch * layer.n_ch
         ref += layer.hw * layer.n_ch * layer.n_ch
+    if layer.kind == 3:
+        # deep sigmoidal (n_ch components of hw hidden units): c = a x + b and w sigmoid(c) per unit -- the transcendental
+        # work (about 60 vector instructions per unit, forward) is not a multiply-add and is not counted; the Linear layer
+        # above is executed once per pass over the tiles (two passes above hidden_dim 4, csrc/tfk_glow_dsf.hip)
+        units = layer.T * layer.n_ch * layer.hw
+        macs += 2 * units + (16 * layer.n_params if layer.hw > 4 else 0)
+        ref += 2 * units
     return dict(bytes=4 * (S + 2 * layer.T) + 8, flops=2 * macs, flops_reference=2 * ref)
 
 
@@ -232,7 +239,9 @@ class _Builder:
     # -- couplings: one launch each --------------------------------------------------------------------------------
     def coupling(self, layer, d: int, M: torch.Tensor) -> None:
         kind = layer.transformer.native_kind
-        if kind not in ("affine", "shift", "conv1x1") or layer.context_shape is not None:
+        if kind == "dsf" and not native._dsf_native(layer.transformer):      # (a size without a kernel, or dsf=0)
+            raise _Decline("no fused kernel for this deep sigmoidal size")
+        if kind not in ("affine", "shift", "conv1x1", "dsf") or layer.context_shape is not None:
             raise _Decline(f"no fused kernel for transformer kind {kind!r}")
         cs = tuple(layer.coupling.constant_shape)
         if len(cs) != 3:
@@ -250,6 +259,10 @@ class _Builder:
             hw = T // n_ch
             if pk["n_params"] != n_ch + n_ch * (n_ch - 1):
                 raise _Decline("unexpected LU parameter count")
+        elif kind == "dsf":                                # (carried where the 1x1 convolution has channels / pixels)
+            n_ch, hw = int(layer.transformer.n_components), int(layer.transformer.hidden_dim)
+            if pk["n_params"] != T * 3 * hw * n_ch:
+                raise _Decline("unexpected deep sigmoidal parameter count")
         elif pk["n_params"] != (T if kind == "shift" else 2 * T):
             raise _Decline("unexpected parameter count")
         if int(src.numel()) != c_in * hi * wi:
@@ -294,13 +307,31 @@ class _Builder:
             W4[:2 * T] = (pk["W_eff"].view(T, 2, 16)[order] * log2e).reshape(2 * T, 16)
             b4[:2 * T] = (pk["b_eff"].view(T, 2)[order] * log2e).reshape(2 * T)
             aux.update(tgt=tgt_k.clone(), W4=W4.float().contiguous(), b4=b4.float().contiguous())
+        elif kind == "dsf":
+            # tile order: target group (16 neighbours in the row), then parameter, then target within the group -- row
+            # (m P + p) 16 + j is parameter p = h[..., t, p] of the target at position 16 m + j of the sorted list
+            order = torch.argsort(tgt, stable=True)
+            tgt_k = tgt[order]
+            P = 3 * hw * n_ch
+            n_groups = (T + 15) // 16
+            rank = torch.arange(T)
+            rows_k = ((rank // 16 * P)[:, None] + torch.arange(P)[None, :]) * 16 + (rank % 16)[:, None]     # (T, P)
+            Wk = torch.zeros(n_groups * P * 16, 16, dtype=torch.float64)
+            bk = torch.zeros(n_groups * P * 16, dtype=torch.float64)
+            Wk[rows_k.reshape(-1)] = pk["W_eff"].view(T, P, 16)[order].reshape(T * P, 16)
+            bk[rows_k.reshape(-1)] = pk["b_eff"].view(T, P)[order].reshape(T * P)
+            w_tiles, b_tiles = _tile_pack(Wk, bk)
+            pad = (-T) % 64
+            tgt_i = torch.cat([tgt_k.to(torch.int32), torch.zeros(pad, dtype=torch.int32)])
+            tgt_m = torch.cat([st(tgt_k), torch.zeros(pad, 2)])
+            aux.update(tgt=tgt_k.clone())
         else:
             w_tiles, b_tiles = _tile_pack(pk["W_eff"], pk["b_eff"])
             tgt_i, tgt_m = tgt.to(torch.int32), st(tgt)
         keep = (src.to(torch.int32).to(dev), st(src).to(dev), tgt_i.to(dev), tgt_m.to(dev),
                 pk["weights"].to(dev), pk["bg1"].to(dev), pk["bg2"].to(dev), w_tiles.to(dev), b_tiles.to(dev))
         env = lambda k: int(debug_switch("glow_" + k.lower(), "0") or 0)
-        L = native.GlowLayer(kind={"affine": 0, "conv1x1": 1, "shift": 2}[kind], c_in=c_in, hi=hi, wi=wi, oy=pk["oy"], ox=pk["ox"],
+        L = native.GlowLayer(kind={"affine": 0, "conv1x1": 1, "shift": 2, "dsf": 3}[kind], c_in=c_in, hi=hi, wi=wi, oy=pk["oy"], ox=pk["ox"],
                              kh=pk["kh"], kw=pk["kw"], T=T, n_params=pk["n_params"], n_ch=n_ch, hw=hw, slots=env("SLOTS"), block=env("BLOCK"),
                              cg1=env("CG1"), cg2=env("CG2"), grid=env("GRID"),
                              src_idx=keep[0].data_ptr(), src_st=keep[1].data_ptr(), tgt_idx=keep[2].data_ptr(),
@@ -369,6 +400,8 @@ def build_levels(steps: List[Step], D: int, device: torch.device) -> Optional[Li
     level does not fit the level kernel (then the program keeps one launch per step)."""
     import ctypes as C
     env = lambda k: int(debug_switch("glow_level_" + k.lower(), "0") or 0)
+    if any(step.info["kind"] == "dsf" for step in steps):       # (tfk_glow_level has no deep sigmoidal stage)
+        return None
     groups, foot = [], None
     for i, step in enumerate(steps):
         aux = step.info["aux"]
@@ -427,6 +460,23 @@ def compile_program(module, d: int, device: torch.device) -> Optional[ImageProgr
     flush = torch.stack([b.s, b.t], dim=1).float().contiguous().to(device) if pending else None
     levels = build_levels(b.steps, D, device) if levels_enabled() else None
     return ImageProgram(D, b.steps, b.ld, flush, fused._params_version(module), levels)
+
+
+def fills_device(prog: ImageProgram, n_rows: int, d: int, device: torch.device) -> bool:
+    """Is the program the faster route for ``n_rows`` rows?  A deep sigmoidal coupling launch has ONE workgroup walk all
+    target groups of its 16 samples, so its time has a floor set by T and K whatever the batch, while the layer-by-layer
+    kernels spread N * T elements over the device.  Measured on MI355X (T = 1 536 / K = 15 and
+    T = 392 / K = 10 models): the program wins from 8 rows per CU forward and 16 rows per CU inverse (one 16-sample
+    tile per CU); with T <= 96 it wins at every batch size.  ``TORCHFLOWS_AMD_DEBUG="glow_dsf=program"`` (or ``layers``)
+    takes the decision away (tests of the kernel at partial tiles, comparison runs)."""
+    big = max((s.layer.T for s in prog.steps if s.info["kind"] == "dsf"), default=0)
+    forced = debug_switch("glow_dsf", "")
+    if big <= 128 or forced == "program":
+        return True
+    if forced == "layers" or device.type != "cuda":
+        return forced != "layers"
+    cus = torch.cuda.get_device_properties(device).multi_processor_count
+    return n_rows >= (16 if d == INVERSE else 8) * cus
 
 
 def get_program(module, d: int, device: torch.device) -> Optional[ImageProgram]:
