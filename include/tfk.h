@@ -608,6 +608,24 @@ int tfk_convnet_train_linear_wgrad(const float *g, const float *a16, const float
  * per element, as tfk_dsf_coupling_inv); tfk_glow_level does not take it.  The kind adds no field and TFK_ABI_VERSION stays
  * 29, so the version does not tell whether a library has it: probe with tfk_glow_plan on a layer of kind = 3 (no device
  * needed), which a library without the kind answers with TFK_EINVAL.
+ * Kinds 4 and 6 = 4 | transformer kind: the affine (4) and shift (6) couplings whose conditioner is the ResNet
+ * (multiscale/conditioning/resnet.py:62-139: ConvModifier, three stages x + relu(bn2(conv2(relu(bn1(conv1(x)))))) of C -> 16
+ * -> C channels, C = 4, 8, 16, each followed by a stride-2 convolution C -> 2 C, then Linear(512, 100), leaky_relu,
+ * Linear(100, n_params)), forward and inverse, same tables, pending maps and log-det as kinds 0 and 2.  They add no
+ * field and no function either -- probe with tfk_glow_plan as for kind 3 -- and re-use the pointers:
+ *   weights  4 * c_in * kh * kw + 4 + 14 244 floats (tfk_glow_weight_floats keeps counting the ConvNet's): the first ConvModifier
+ *            as above, then per stage conv1 W as [ci=C][3][3][co=16], b1 (16), conv2 W as [ci=16][3][3][co=C], b2 (C), the
+ *            stride-2 convolution's W as [ci=C][3][3][co=2 C], its bias (2 C) -- 18 C^2 + 291 C + 16 floats per stage;
+ *            BatchNorm (in front of the ReLU here) folded into conv1 / conv2: W' = scale W, b' = scale b + shift
+ *   bg1      linear1 in MFMA tile order, 16-byte aligned: 7 tiles x 32 K blocks x [64 lanes][4] floats, tile t, block kb,
+ *            lane l, k-step ks = W1[16 t + (l & 15)][16 kb + 4 (l >> 4) + ks] (rows 100 .. 111 zero), then its bias
+ *            padded to 112 floats.  No background image exists for this conditioner
+ *   bg2      null
+ *   w_eff    linear2 in the row order of kinds 0 and 2, K = 100: per tile 7 K blocks x [64 lanes][4] floats, block kb, lane l,
+ *            k-step ks = W[16 t + (l & 15)][16 kb + 4 ks + (l >> 4)] times log2(e), columns 100 .. 111 zero
+ *   b_eff    16 * tiles floats: log2(e) times linear2's bias in the same row order
+ * They run in workgroups of 256 threads (block = 0 or 256) with slots = 1 .. 3 resident samples (0 = 3, what the LDS
+ * holds); cg1 / cg2 are ignored; tfk_glow_level refuses them.
  * tgt_idx (affine, shift, deep sigmoidal) may list the targets in any order -- ascending physical position makes the 16 targets of a tile pair
  * neighbours in the row -- padded, like tgt_st, to a multiple of 16 entries.
  * Supported: first ConvModifier as the reference builds it for images up to 32 pixels (classic.py:21-33: kernel 1 and padding
@@ -616,7 +634,8 @@ int tfk_convnet_train_linear_wgrad(const float *g, const float *a16, const float
  * slots / block / cg1 / cg2 / grid = 0 let the library choose the launch shape (tfk_glow_plan reports it). */
 typedef struct tfk_glow_layer {
     int32_t kind;              /* 0 affine, 1 invertible 1x1 convolution, 2 shift (z = x +/- h, log-det 0; affine.py:137-159),
-                                * 3 deep sigmoidal (Sigmoid / DeepSigmoid, transformers/combination/sigmoid.py) */
+                                * 3 deep sigmoidal (Sigmoid / DeepSigmoid, transformers/combination/sigmoid.py),
+                                * 4 affine and 6 shift behind the ResNet conditioner */
     int32_t c_in, hi, wi;      /* conditioner input image */
     int32_t oy, ox;            /* where the modifier's non-constant rectangle starts in its 32x32 frame: padding - (kernel - 1) */
     int32_t kh, kw;            /* first ConvModifier's kernel, 1 or 2 per axis (0 = 1); the rectangle is (hi + kh - 1, wi + kw - 1) */

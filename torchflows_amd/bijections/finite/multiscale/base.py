@@ -8,7 +8,9 @@ index lists instead of the contiguous tail; the channel-wise split IS a contiguo
 the 1x1 convolution is ``tfk_conv1x1_coupling``; ``Squeeze`` is a fixed permutation of the
 flattened event and runs as ``tfk_permute``.  The ConvNet conditioner runs on libtfk too: folded into
 one launch per coupling at inference (image_program.py), one launch per block with gradients or batch
-statistics (convnet_train.py); only conditioners of another shape stay on PyTorch-ROCm (MIOpen).
+statistics (convnet_train.py); only conditioners of another shape stay on PyTorch-ROCm (MIOpen).  The ResNet
+conditioner (``conditioner="resnet"``, ``MultiscaleBijection(use_resnet=True)``) is one launch per affine / shift
+coupling at inference too (csrc/tfk_glow_resnet.hip) and runs on ATen otherwise.
 
 Reference quirk kept: the recursive ``small_bijection`` does not inherit
 ``checkerboard_class`` / ``channel_wise_class`` / ``n_*_layers`` / ``use_resnet``, and the
@@ -30,6 +32,7 @@ from torchflows_amd.bijections.finite.autoregressive.transformers.base import Te
 from torchflows_amd.bijections.finite.autoregressive.transformers.linear.convolution import (
     Invertible1x1ConvolutionTransformer)
 from torchflows_amd.bijections.finite.multiscale.conditioning.classic import ConvNetConditioner
+from torchflows_amd.bijections.finite.multiscale.conditioning.resnet import ResNetConditioner
 from torchflows_amd.bijections.finite.multiscale.coupling import (
     ChannelWiseHalfSplit, Checkerboard, make_image_coupling)
 from torchflows_amd.utils import get_batch_shape
@@ -39,11 +42,14 @@ class ConvolutionalCouplingBijection(CouplingBijection):
     def __init__(self, event_shape, transformer_class: Type[TensorTransformer],
                  coupling: Union[Checkerboard, ChannelWiseHalfSplit], conditioner: str = "convnet",
                  **kwargs):
-        if conditioner != "convnet":
-            # the ResNet conditioner is outside this package's scope
+        if conditioner == "convnet":
+            conditioner_class = ConvNetConditioner
+        elif conditioner == "resnet":
+            conditioner_class = ResNetConditioner
+        else:
             raise ValueError(f"Unknown conditioner: {conditioner}")
         super().__init__(event_shape=event_shape, transformer_class=transformer_class,
-                         coupling=coupling, conditioner_transform_class=ConvNetConditioner, **kwargs)
+                         coupling=coupling, conditioner_transform_class=conditioner_class, **kwargs)
 
 
 class CheckerboardCoupling(ConvolutionalCouplingBijection):
@@ -143,7 +149,10 @@ class Squeeze(Bijection):
 
 class MultiscaleBijection(Bijection):
     """checkerboard couplings -> squeeze -> channel-wise couplings -> unsqueeze -> squeeze,
-    keep half of the channels, recurse on the other half -> unsqueeze (reference :178-296)."""
+    keep half of the channels, recurse on the other half -> unsqueeze (reference :178-296).
+
+    ``use_resnet=True`` gives the couplings of THIS block the ResNet conditioner; the recursive ``small_bijection``
+    is built without the keyword (the reference's quirk) and keeps the ConvNet."""
 
     def __init__(self, event_shape, transformer_class: Type[TensorTransformer], n_blocks: int,
                  n_checkerboard_layers: int = 3, n_channel_wise_layers: int = 3,

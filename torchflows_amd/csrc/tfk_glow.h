@@ -310,4 +310,11 @@ int glow_geometry_base(const tfk_glow_layer *L, int32_t D, GlowGeom &g, const ch
 int glow_dsf_launch(float *rows, float *logdet, int64_t N, const GlowGeom &g, int block, size_t lds,
                     const tfk_glow_layer *layer, int inverse, hipStream_t s, const char *fn);
 
+// kinds 4 and 6 (affine / shift behind the ResNet conditioner, tfk_glow_resnet.hip): the geometry behind
+// glow_geometry_base, the launch shape and the launch behind tfk_glow_coupling
+void glow_resnet_geometry(GlowGeom &g);
+bool glow_resnet_plan(GlowGeom &g, int want_slots, int want_block, int *block_out);
+int glow_resnet_launch(float *rows, float *logdet, int64_t N, const GlowGeom &g, int block, size_t lds,
+                       const tfk_glow_layer *layer, int inverse, hipStream_t s, const char *fn);
+
 }  // namespace tfk

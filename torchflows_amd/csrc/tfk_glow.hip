@@ -318,8 +318,10 @@ namespace tfk {
 int glow_geometry_base(const tfk_glow_layer *L, int32_t D, GlowGeom &g, const char *fn)
 {
     if (!L) return fail(TFK_EINVAL, "%s: null layer", fn);
-    if (L->kind < 0 || L->kind > 3)
-        return fail(TFK_EINVAL, "%s: kind %d (0 affine, 1 invertible 1x1 convolution, 2 shift, 3 deep sigmoidal)", fn, L->kind);
+    if (L->kind < 0 || (L->kind > 3 && L->kind != 4 && L->kind != 6))
+        return fail(TFK_EINVAL, "%s: kind %d (0 affine, 1 invertible 1x1 convolution, 2 shift, 3 deep sigmoidal; 4 affine and "
+                    "6 shift behind the ResNet conditioner)", fn, L->kind);
+    const int tk = L->kind & 3;                         // the transformer's kind
     const int kh = L->kh > 0 ? L->kh : 1, kw = L->kw > 0 ? L->kw : 1;
     if (kh > 2 || kw > 2) return fail(TFK_EINVAL, "%s: modifier kernel %dx%d (1 or 2 per axis)", fn, kh, kw);
     if (L->c_in < 1 || L->hi < 1 || L->wi < 1 || L->oy < 0 || L->ox < 0 || L->oy + L->hi + kh - 1 > kGlowFrame ||
@@ -327,9 +329,9 @@ int glow_geometry_base(const tfk_glow_layer *L, int32_t D, GlowGeom &g, const ch
         return fail(TFK_EINVAL, "%s: source image (%d, %d, %d), kernel %dx%d, at (%d, %d) does not fit the %dx%d frame", fn,
                     L->c_in, L->hi, L->wi, kh, kw, L->oy, L->ox, kGlowFrame, kGlowFrame);
     if (L->T < 1 || L->n_params < 1 || D < 1) return fail(TFK_EINVAL, "%s: T = %d, n_params = %d, D = %d", fn, L->T, L->n_params, D);
-    if (L->kind == 2 && L->n_params != L->T)
+    if (tk == 2 && L->n_params != L->T)
         return fail(TFK_EINVAL, "%s: a shift coupling of %d targets takes %d parameters, got %d", fn, L->T, L->T, L->n_params);
-    if (L->kind == 0 && L->n_params != 2 * L->T)
+    if (tk == 0 && L->n_params != 2 * L->T)
         return fail(TFK_EINVAL, "%s: an affine coupling of %d targets takes %d parameters, got %d", fn, L->T, 2 * L->T, L->n_params);
     if (L->kind == 1 && (L->n_ch < 1 || L->n_ch > kGlowMaxCh || L->hw < 1 || L->n_ch * L->hw != L->T ||
                          L->n_params != L->n_ch + L->n_ch * (L->n_ch - 1)))
@@ -344,12 +346,13 @@ int glow_geometry_base(const tfk_glow_layer *L, int32_t D, GlowGeom &g, const ch
     g.c_in = L->c_in, g.hi = L->hi, g.wi = L->wi, g.oy = L->oy, g.ox = L->ox;
     g.kh = kh, g.kw = kw, g.rh = L->hi + kh - 1, g.rw = L->wi + kw - 1, g.cm = L->c_in * kh * kw;
     g.T = L->T, g.n_params = L->n_params, g.D = D;
-    g.n_tiles = L->kind == 0 ? 2 * ((L->T + 15) / 16) : (L->n_params + 15) / 16;        // (shift: one tile per 16 targets)
+    g.n_tiles = tk == 0 ? 2 * ((L->T + 15) / 16) : (L->n_params + 15) / 16;        // (shift: one tile per 16 targets)
     if (L->kind == 3) g.n_tiles = 3 * L->hw * L->n_ch * ((L->T + 15) / 16);             // (3 K C tiles per 16 targets)
     g.kind = L->kind, g.n_ch = L->n_ch, g.hw = L->hw;
     g.h_stride = g.n_tiles * 16 + 1;
     g.fixed_floats = 512 + (L->kind == 1 ? ((kGlowMaxRows * g.h_stride + 3) & ~3) : 0);
-    glow_windows(g);
+    if (L->kind & 4) glow_resnet_geometry(g);
+    else glow_windows(g);
     {
         const char *e = getenv("TFK_GLOW_SKIP");
         g.skip = e ? atoi(e) : 0;
@@ -365,7 +368,7 @@ int glow_geometry(const tfk_glow_layer *L, int32_t D, GlowGeom &g, int *block, c
 {
     const int rc = glow_geometry_base(L, D, g, fn);
     if (rc != TFK_OK) return rc;
-    if (!glow_plan(g, L->slots, L->block, L->cg1, L->cg2, block))
+    if (L->kind & 4 ? !glow_resnet_plan(g, L->slots, L->block, block) : !glow_plan(g, L->slots, L->block, L->cg1, L->cg2, block))
         return fail(TFK_EINVAL, "%s: no launch shape fits (slots %d, block %d, channel groups %d / %d; %d B per slot)",
                     fn, L->slots, L->block, L->cg1, L->cg2, 4 * g.slot_floats);
     if (L->kind == 3 && *block > 256)
@@ -406,7 +409,7 @@ int tfk_glow_coupling(float *rows, float *logdet, int64_t N, int32_t D, const tf
     if (rc != TFK_OK) return rc;
     if (N == 0) return TFK_OK;
     if (!rows || !logdet || !layer->src_idx || !layer->src_st || !layer->tgt_idx || !layer->tgt_st || !layer->weights ||
-        !layer->bg1 || !layer->bg2 || !layer->w_eff || !layer->b_eff)
+        !layer->bg1 || (!layer->bg2 && !(layer->kind & 4)) || !layer->w_eff || !layer->b_eff)
         return fail(TFK_EINVAL, "%s: null pointer", fn);
     if (!aligned16(layer->w_eff) || !aligned16(layer->b_eff) || (reinterpret_cast<uintptr_t>(layer->tgt_st) & 7u) ||
         (reinterpret_cast<uintptr_t>(layer->src_st) & 7u))
@@ -434,6 +437,8 @@ int tfk_glow_coupling(float *rows, float *logdet, int64_t N, int32_t D, const tf
     } while (0)
     if (layer->kind == 3)                  // (tfk_glow_dsf.hip: its own kernels, grid from their occupancy)
         return glow_dsf_launch(rows, logdet, N, g, block, lds, layer, inverse, s, fn);
+    if (layer->kind & 4)                   // (tfk_glow_resnet.hip: the ResNet conditioner)
+        return glow_resnet_launch(rows, logdet, N, g, block, lds, layer, inverse, s, fn);
     if (layer->kind == 0 && !inverse) TFK_GLOW(0, false);
     else if (layer->kind == 0) TFK_GLOW(0, true);
     else if (layer->kind == 2 && !inverse) TFK_GLOW(2, false);

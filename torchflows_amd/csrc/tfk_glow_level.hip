@@ -546,6 +546,8 @@ int level_plan(const tfk_glow_level_step *steps, int32_t n_steps, int32_t D, int
         if (rc != TFK_OK) return rc;
         if (g.kind == 3)
             return fail(TFK_EINVAL, "%s: step %d is a deep sigmoidal coupling; it runs as its own tfk_glow_coupling launch", fn, i);
+        if (g.kind & 4)
+            return fail(TFK_EINVAL, "%s: step %d has the ResNet conditioner; it runs as its own tfk_glow_coupling launch", fn, i);
         if (g.slot_floats > 65535) return fail(TFK_EINVAL, "%s: activation buffers of %d floats per sample", fn, g.slot_floats);
         const int cg1 = steps[i].layer.cg1 ? steps[i].layer.cg1 : 4, cg2 = steps[i].layer.cg2 ? steps[i].layer.cg2 : 4;
         if ((cg1 != 8 && cg1 != 4 && cg1 != 2) || (cg2 != 8 && cg2 != 4 && cg2 != 2))

@@ -18,6 +18,10 @@ recursion is *compiled* once per parameter version into a flat list of ``tfk_glo
   (``bg1`` / ``bg2``), the second ConvModifier + BatchNorm 3 + the 84 constant inputs of the Linear layer folded into a
   ``(n_params, 16)`` matrix in MFMA tile order.
 
+The ResNet conditioner (``use_resnet=True``, the outermost block's couplings) is folded likewise for affine and shift
+couplings: BatchNorm sits in front of the ReLU there, so it goes into the convolutions themselves
+(``_pack_resnet_conditioner``; kinds 4 and 6 of ``tfk_glow_coupling``, csrc/tfk_glow_resnet.hip).
+
 A model the compiler does not cover (another conditioner, a modifier that is a real convolution -- images larger than 32
 pixels --, a transformer other than Affine / Shift / the 1x1 convolution / Sigmoid and DeepSigmoid, a context, ``invert()``-ed layers, an
 ActNorm that still waits for its first batch) returns None and runs layer by layer as before.
@@ -70,6 +74,10 @@ class ImageProgram:
 
 class _Decline(Exception):
     pass
+
+
+class _DeclineLoud(_Decline):
+    """A decline the user is told about (NativeRouteWarning): the layer-by-layer route is much slower there."""
 
 
 def enabled() -> bool:
@@ -165,18 +173,76 @@ def _pack_conditioner(cond, c_in: int, hi: int, wi: int):
 
 
 def _tile_pack(W_rows: torch.Tensor, b_rows: torch.Tensor):
-    """(rows, 16) / (rows,) in kernel row order -> MFMA operand tiles [t][64 lanes][4 k-steps] and the padded bias, both
-    multiplied by log2(e):
-    tile t, lane l = 16 q + i, k-step ks  <-  W[16 t + i][4 ks + q]."""
-    n = W_rows.shape[0]
-    n_tiles = (n + 15) // 16
+    """(rows, K) / (rows,) in kernel row order -> MFMA operand tiles [t][K / 16 blocks][64 lanes][4 k-steps] and the padded
+    bias, both multiplied by log2(e):
+    tile t, block kb, lane l = 16 q + i, k-step ks  <-  W[16 t + i][16 kb + 4 ks + q]
+    (K = 16, the ConvNet conditioner: one block; K = 100, the ResNet's linear2: seven, columns of padding zero)."""
+    n, K = W_rows.shape
+    n_tiles, n_kb = (n + 15) // 16, (K + 15) // 16
     log2e = 1.4426950408889634          # the kernel's sigmoid is 1 / (1 + exp2(-h')): h' = h log2(e)
-    Wp = torch.zeros(n_tiles * 16, 16, dtype=torch.float64)
-    Wp[:n] = W_rows * log2e
+    Wp = torch.zeros(n_tiles * 16, n_kb * 16, dtype=torch.float64)
+    Wp[:n, :K] = W_rows * log2e
     bp = torch.zeros(n_tiles * 16, dtype=torch.float64)
     bp[:n] = b_rows * log2e
-    w_tiles = Wp.view(n_tiles, 16, 4, 4).permute(0, 3, 1, 2).reshape(-1)
+    w_tiles = Wp.view(n_tiles, 16, n_kb, 4, 4).permute(0, 2, 4, 1, 3).reshape(-1)
     return w_tiles.float().contiguous(), bp.float().contiguous()
+
+
+def _fold_bn(conv: nn.Conv2d, bn: nn.BatchNorm2d):
+    """Inference BatchNorm behind a convolution, folded into it (float64): W' = scale W, b' = scale b + shift."""
+    scale, shift = _bn_affine(bn)
+    W, b = conv.weight.detach().double().cpu(), conv.bias.detach().double().cpu()
+    return W * scale.view(-1, 1, 1, 1), b * scale + shift
+
+
+def _pack_resnet_conditioner(cond, c_in: int, hi: int, wi: int):
+    """Host-side (float64) folding of a ResNetConditioner for kinds 4 and 6 of tfk_glow_coupling (include/tfk.h): the
+    modifier as for the ConvNet, then per stage conv1 / conv2 with their BatchNorms folded in and the stride-2
+    convolution, all as [ci][ky][kx][co]; linear1 in MFMA tile order (``bg1``); linear2 as W_eff / b_eff."""
+    from torchflows_amd.bijections.finite.multiscale.conditioning.classic import ConvModifier
+    from torchflows_amd.bijections.finite.multiscale.conditioning.resnet import ResNet
+    if cond.n_global_parameters != 0 or cond.context_shape is not None:
+        raise _Decline("ResNet conditioner with a context or global parameters")
+    if cond.output_lower_bound != -2.0 or cond.output_upper_bound != 2.0:
+        raise _Decline("conditioner bounds are not (-2, 2)")
+    net = cond.network
+    if not isinstance(net, ResNet) or not isinstance(net.modifier, ConvModifier):
+        raise _Decline("unexpected ResNet layout")
+    stages = ((net.stage1, net.down1, 4), (net.stage2, net.down2, 8), (net.stage3, net.down3, 16))
+    if any(len(stage.blocks) != 1 for stage, _, _ in stages):
+        raise _Decline("ResNet n_blocks is not (1, 1, 1)")
+    if tuple(net.linear1.weight.shape) != (100, 512) or net.linear2.in_features != 100:
+        raise _Decline("ResNet hidden size is not 100")
+    c1 = net.modifier.conv
+    kh, kw = (int(k) for k in c1.kernel_size)
+    if kh > 2 or kw > 2 or tuple(c1.weight.shape) != (4, c_in, kh, kw) or hi > 32 or wi > 32:
+        raise _Decline("first ConvModifier is not a padding convolution onto (4, 32, 32)")
+    py, px = (int(p) for p in c1.padding)
+    if (hi + 2 * py - kh + 1 != 32 or wi + 2 * px - kw + 1 != 32 or py < kh - 1 or px < kw - 1
+            or tuple(c1.stride) != (1, 1) or tuple(c1.dilation) != (1, 1) or c1.bias is None):
+        raise _Decline("first ConvModifier does not produce a 32x32 frame")
+    dd = lambda t: t.detach().double().cpu()
+    khwc = lambda W: W.permute(1, 2, 3, 0).reshape(-1)                  # [ci][ky][kx][co]
+    parts = [dd(c1.weight).reshape(-1), dd(c1.bias)]
+    for stage, down, C in stages:
+        blk, cd = stage.blocks[0], down.conv2d
+        if (tuple(blk.conv1.weight.shape) != (16, C, 3, 3) or tuple(blk.conv2.weight.shape) != (C, 16, 3, 3)
+                or tuple(cd.weight.shape) != (2 * C, C, 3, 3) or tuple(cd.stride) != (2, 2) or tuple(cd.padding) != (1, 1)
+                or blk.conv1.bias is None or blk.conv2.bias is None or cd.bias is None):
+            raise _Decline("residual stages are not the default C -> 16 -> C blocks with a stride-2 convolution")
+        W1, b1 = _fold_bn(blk.conv1, blk.bn1)
+        W2, b2 = _fold_bn(blk.conv2, blk.bn2)
+        parts += [khwc(W1), b1, khwc(W2), b2, khwc(dd(cd.weight)), dd(cd.bias)]
+    weights = torch.cat(parts).float()
+    assert weights.numel() == native.glow_resnet_weight_floats(c_in * kh * kw)
+    # linear1: tile t, K block kb, lane 16 q + i, k-step ks  <-  W[16 t + i][16 kb + 4 q + ks]; then the bias, 112 floats
+    W1p = torch.zeros(112, 512, dtype=torch.float64)
+    W1p[:100] = dd(net.linear1.weight)
+    b1p = torch.zeros(112, dtype=torch.float64)
+    b1p[:100] = dd(net.linear1.bias)
+    lin1 = torch.cat([W1p.view(7, 16, 32, 4, 4).permute(0, 2, 3, 1, 4).reshape(-1), b1p]).float().contiguous()
+    return dict(oy=py - (kh - 1), ox=px - (kw - 1), kh=kh, kw=kw, n_params=int(net.linear2.weight.shape[0]),
+                weights=weights, bg1=lin1, bg2=None, W_eff=dd(net.linear2.weight), b_eff=dd(net.linear2.bias))
 
 
 def layer_cost(layer) -> dict:
@@ -192,6 +258,11 @@ def layer_cost(layer) -> dict:
     kh, kw = max(layer.kh, 1), max(layer.kw, 1)
     (c1h, c2h), (c1w, c2w) = axis(layer.oy, layer.hi + kh - 1), axis(layer.ox, layer.wi + kw - 1)
     S = layer.c_in * layer.hi * layer.wi
+    if layer.kind & 4:       # ResNet conditioner (csrc/tfk_glow_resnet.hip): full frames, as the reference computes them
+        trunk = sum(2 * hw * hw * 144 * C + (hw // 2) ** 2 * 18 * C * C for C, hw in ((4, 32), (8, 16), (16, 8)))
+        macs = 4 * S * kh * kw + trunk + 512 * 100 + 100 * layer.n_params
+        ref = 4 * 1024 * layer.c_in * kh * kw + trunk + 512 * 100 + 100 * layer.n_params
+        return dict(bytes=4 * (S + 2 * layer.T) + 8, flops=2 * macs, flops_reference=2 * ref)
     macs = 4 * S * kh * kw + c1h * c1w * 8 * 36 + c2h * c2w * 8 * 72 + 64 * 4 * 72 + 64 + 16 * layer.n_params
     ref = 4 * 1024 * layer.c_in * kh * kw + 1024 * 8 * 36 + 256 * 8 * 72 + 64 * 4 * 72 + 16 * 4 + 100 * layer.n_params
     if layer.kind == 1:
@@ -247,7 +318,15 @@ class _Builder:
         if len(cs) != 3:
             raise _Decline("conditioner input is not an image")
         c_in, hi, wi = (int(v) for v in cs)
-        pk = _pack_conditioner(layer.conditioner_transform, c_in, hi, wi)
+        from torchflows_amd.bijections.finite.multiscale.conditioning.resnet import ResNetConditioner
+        resnet = isinstance(layer.conditioner_transform, ResNetConditioner)
+        if resnet and kind == "dsf":
+            # (its linear2 would be 100 x 46 080 at (3, 32, 32): no launch holds it)
+            raise _DeclineLoud("a deep sigmoidal coupling behind the ResNet conditioner has no fused launch")
+        if resnet and kind not in ("affine", "shift"):
+            raise _Decline(f"no fused kernel for transformer kind {kind!r} behind the ResNet conditioner")
+        pk = (_pack_resnet_conditioner if resnet else _pack_conditioner)(layer.conditioner_transform, c_in, hi, wi)
+        K = int(pk["W_eff"].shape[1])                      # the Linear layer's inputs: 16 (ConvNet) or 100 (ResNet)
         src = M[layer._source_index.cpu()]
         tgt = M[layer._target_index.cpu()]
         T = int(tgt.numel())
@@ -280,7 +359,7 @@ class _Builder:
             tgt_i = torch.cat([tgt_k.to(torch.int32), torch.zeros(pad, dtype=torch.int32)])
             tgt_m = torch.cat([st(tgt_k), torch.zeros(pad, 2)])
             R = T + pad
-            W4 = torch.zeros(R, 16, dtype=torch.float64)
+            W4 = torch.zeros(R, K, dtype=torch.float64)
             b4 = torch.zeros(R, dtype=torch.float64)
             W4[:T], b4[:T] = pk["W_eff"][order] * log2e, pk["b_eff"][order] * log2e
             aux.update(tgt=tgt_k.clone(), W4=W4.float().contiguous(), b4=b4.float().contiguous())
@@ -292,7 +371,7 @@ class _Builder:
             n_groups = (T + 15) // 16
             rank = torch.arange(T)
             row_u = 32 * (rank // 16) + rank % 16
-            Wk = torch.zeros(32 * n_groups, 16, dtype=torch.float64)
+            Wk = torch.zeros(32 * n_groups, K, dtype=torch.float64)
             bk = torch.zeros(32 * n_groups, dtype=torch.float64)
             Wk[row_u], bk[row_u] = pk["W_eff"][2 * order], pk["b_eff"][2 * order]
             Wk[row_u + 16], bk[row_u + 16] = pk["W_eff"][2 * order + 1], pk["b_eff"][2 * order + 1]
@@ -302,9 +381,9 @@ class _Builder:
             tgt_m = torch.cat([st(tgt_k), torch.zeros(pad, 2)])
             # the level kernel's operands: rows [u of target 0, beta of target 0, u of target 1, ...] in sorted order
             R = 2 * (T + pad)
-            W4 = torch.zeros(R, 16, dtype=torch.float64)
+            W4 = torch.zeros(R, K, dtype=torch.float64)
             b4 = torch.zeros(R, dtype=torch.float64)
-            W4[:2 * T] = (pk["W_eff"].view(T, 2, 16)[order] * log2e).reshape(2 * T, 16)
+            W4[:2 * T] = (pk["W_eff"].view(T, 2, K)[order] * log2e).reshape(2 * T, K)
             b4[:2 * T] = (pk["b_eff"].view(T, 2)[order] * log2e).reshape(2 * T)
             aux.update(tgt=tgt_k.clone(), W4=W4.float().contiguous(), b4=b4.float().contiguous())
         elif kind == "dsf":
@@ -329,17 +408,18 @@ class _Builder:
             w_tiles, b_tiles = _tile_pack(pk["W_eff"], pk["b_eff"])
             tgt_i, tgt_m = tgt.to(torch.int32), st(tgt)
         keep = (src.to(torch.int32).to(dev), st(src).to(dev), tgt_i.to(dev), tgt_m.to(dev),
-                pk["weights"].to(dev), pk["bg1"].to(dev), pk["bg2"].to(dev), w_tiles.to(dev), b_tiles.to(dev))
+                pk["weights"].to(dev), pk["bg1"].to(dev), None if resnet else pk["bg2"].to(dev), w_tiles.to(dev),
+                b_tiles.to(dev))
         env = lambda k: int(debug_switch("glow_" + k.lower(), "0") or 0)
-        L = native.GlowLayer(kind={"affine": 0, "conv1x1": 1, "shift": 2, "dsf": 3}[kind], c_in=c_in, hi=hi, wi=wi, oy=pk["oy"], ox=pk["ox"],
+        L = native.GlowLayer(kind={"affine": 0, "conv1x1": 1, "shift": 2, "dsf": 3}[kind] | (4 if resnet else 0), c_in=c_in, hi=hi, wi=wi, oy=pk["oy"], ox=pk["ox"],
                              kh=pk["kh"], kw=pk["kw"], T=T, n_params=pk["n_params"], n_ch=n_ch, hw=hw, slots=env("SLOTS"), block=env("BLOCK"),
                              cg1=env("CG1"), cg2=env("CG2"), grid=env("GRID"),
                              src_idx=keep[0].data_ptr(), src_st=keep[1].data_ptr(), tgt_idx=keep[2].data_ptr(),
                              tgt_st=keep[3].data_ptr(), weights=keep[4].data_ptr(), bg1=keep[5].data_ptr(),
-                             bg2=keep[6].data_ptr(), w_eff=keep[7].data_ptr(), b_eff=keep[8].data_ptr())
+                             bg2=None if resnet else keep[6].data_ptr(), w_eff=keep[7].data_ptr(), b_eff=keep[8].data_ptr())
         plan = native.glow_plan(L, self.D)                # validates the shape (raises NativeError otherwise)
         self.steps.append(Step(L, d == INVERSE, keep,
-                               dict(kind=kind, image=(c_in, hi, wi), at=(pk["oy"], pk["ox"]), T=T, aux=aux, **plan)))
+                               dict(kind=kind + "_resnet" if resnet else kind, image=(c_in, hi, wi), at=(pk["oy"], pk["ox"]), T=T, aux=aux, **plan)))
         self.s[tgt] = 1.0                                  # targets are stored in final form
         self.t[tgt] = 0.0
 
@@ -400,8 +480,8 @@ def build_levels(steps: List[Step], D: int, device: torch.device) -> Optional[Li
     level does not fit the level kernel (then the program keeps one launch per step)."""
     import ctypes as C
     env = lambda k: int(debug_switch("glow_level_" + k.lower(), "0") or 0)
-    if any(step.info["kind"] == "dsf" for step in steps):       # (tfk_glow_level has no deep sigmoidal stage)
-        return None
+    if any(step.info["kind"] in ("dsf", "affine_resnet", "shift_resnet") for step in steps):
+        return None                                              # (tfk_glow_level has no deep sigmoidal stage and no ResNet)
     groups, foot = [], None
     for i, step in enumerate(steps):
         aux = step.info["aux"]
@@ -452,6 +532,13 @@ def compile_program(module, d: int, device: torch.device) -> Optional[ImageProgr
     try:
         with torch.no_grad():
             _walk(b, module, d, torch.arange(D))
+    except _DeclineLoud as why:
+        if not module.__dict__.get("_tfk_declined_warned"):
+            import warnings
+            module.__dict__["_tfk_declined_warned"] = True
+            warnings.warn(f"torchflows_amd: this image flow runs layer by layer, its conditioners on ATen: {why}",
+                          fused.NativeRouteWarning, stacklevel=4)
+        return None
     except (_Decline, native.NativeError):
         return None
     if not b.steps:

@@ -1098,6 +1098,13 @@ def glow_plan(layer: GlowLayer, D: int) -> dict:
     return dict(zip(("slots", "block", "cg1", "cg2", "lds_bytes", "tile_rows"), (int(v.value) for v in vals)))
 
 
+def glow_resnet_weight_floats(c_in_taps: int) -> int:
+    """Floats of ``tfk_glow_layer.weights`` for kinds 4 and 6 (the formula of include/tfk.h; tfk_glow_weight_floats keeps
+    counting the ConvNet's): modifier W and b, then per stage of C = 4, 8, 16 channels conv1 (C, 16), conv2 (16, C) and
+    the stride-2 convolution (C, 2 C) with their biases."""
+    return 4 * c_in_taps + 4 + sum(18 * C * C + 291 * C + 16 for C in (4, 8, 16))
+
+
 def glow_coupling(rows: torch.Tensor, logdet: torch.Tensor, layer: GlowLayer, inverse: bool = False) -> None:
     """One convolutional coupling in place on the rows (conditioner, bounded output, transform, log-det added)."""
     name = "tfk_glow_coupling"
