@@ -411,7 +411,21 @@ int tfk_lrs_coupling_inv(const float *z, const float *h, float *x, float *logdet
  * f(c) < y, result = the last midpoint) runs inside the launch, per element until the fp32 midpoint stops moving and at
  * most 64 times; the log-det is minus the forward log-det at the returned x.
  * bwd: reverse mode of fwd recomputed from x and h, in place on g at the target columns, gh (N, T, 3 K C) written;
- * inverse != 0 is TFK_EINVAL (the bisection carries no gradient: that direction is differentiated on the ATen path). */
+ * inverse != 0 is TFK_EINVAL (the bisection carries no gradient: that direction is differentiated on the ATen path).
+ *
+ * The DENSE sigmoidal family (DenseSigmoid / DeepDenseSigmoid of the same file; csrc/tfk_dense_dsf.hip) rides on the same
+ * three entry points; no symbol is added and TFK_ABI_VERSION stays.  It is selected by any bit above bit 7 of n_components:
+ *   n_components = C | (L + 1) << 8   C components of L + 2 inner transforms (L = n_dense_layers);  hidden_dim = hidden size H.
+ *   Per element a component takes P = H^2 + 4 H + 3 + L (2 H^2 + 2 H) parameters: per inner transform (i inputs, o outputs;
+ *   1 -> H, L x (H -> H), H -> 1) the vectors [da (o) | db (o) | dw (o o, row-major) | du (o i, row-major)].
+ *   h       the conditioner's PREDICTED block, (N, stride) floats, or NULL when every parameter is a learned constant.  The
+ *           (N, T, C P) parameter tensor is composed inside the launch and never stored.
+ *   tgt_idx never NULL: one int32 device block [T target columns | stride | col (T C P) | base (T C P, float bits)].
+ *           Parameter j of target t of row n is h[n * stride + col[t C P + j]] where col >= 0, else base[t C P + j].
+ *           The kernel does not check it: targets in [0, D), col in [-1, stride).
+ *   Supported (tfk_dsf_supported; anything else is TFK_EINVAL): 1 <= H <= 8, 0 <= L <= 2, C = 1 or 2, C P <= 512.  A
+ *   library without the family answers 0 (C = 0 components there), which is the probe.
+ *   inv: the same bisection, once per component (last to first) over its L + 2 transforms.  bwd: TFK_EINVAL. */
 int tfk_dsf_supported(int32_t n_components, int32_t hidden_dim);
 int tfk_dsf_coupling_fwd(const float *x, const float *h, float *z, float *logdet, int64_t N, int32_t D,
                          const int32_t *tgt_idx, int32_t T, int32_t n_components, int32_t hidden_dim,

@@ -10,7 +10,8 @@ from torchflows_amd.flows import Flow, BaseFlow  # noqa: F401
 from torchflows_amd.bijections.finite.autoregressive.architectures import (  # noqa: F401
     RealNVP, CouplingRQNSF, CouplingLRS, NICE, MAF, IAF, MaskedAutoregressiveRQNSF,
     InverseAutoregressiveRQNSF, MaskedAutoregressiveLRS, InverseAutoregressiveLRS, CouplingDeepSF,
-    MaskedAutoregressiveDeepSF, InverseAutoregressiveDeepSF)
+    MaskedAutoregressiveDeepSF, InverseAutoregressiveDeepSF, CouplingDenseSF, MaskedAutoregressiveDenseSF,
+    InverseAutoregressiveDenseSF, CouplingDeepDenseSF, MaskedAutoregressiveDeepDenseSF, InverseAutoregressiveDeepDenseSF)
 from torchflows_amd.bijections.finite.multiscale.architectures import (  # noqa: F401
     MultiscaleDeepSigmoid, DeepSigmoidGlow)
 

@@ -5,5 +5,6 @@ from torchflows_amd.bijections.finite.autoregressive.architectures import *  # n
 from torchflows_amd.bijections.finite.autoregressive.architectures import (  # noqa: F401
     RealNVP, CouplingRQNSF, CouplingLRS, NICE, MAF, IAF, MaskedAutoregressiveRQNSF,
     InverseAutoregressiveRQNSF, MaskedAutoregressiveLRS, InverseAutoregressiveLRS, CouplingDeepSF,
-    MaskedAutoregressiveDeepSF, InverseAutoregressiveDeepSF)
+    MaskedAutoregressiveDeepSF, InverseAutoregressiveDeepSF, CouplingDenseSF, MaskedAutoregressiveDenseSF,
+    InverseAutoregressiveDenseSF, CouplingDeepDenseSF, MaskedAutoregressiveDeepDenseSF, InverseAutoregressiveDeepDenseSF)
 from torchflows_amd.bijections.finite.multiscale.architectures import *  # noqa: F401,F403

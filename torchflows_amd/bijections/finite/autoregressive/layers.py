@@ -16,6 +16,8 @@ from torchflows_amd.bijections.finite.autoregressive.transformers.linear.affine 
     Affine, InverseAffine, Scale, Shift)
 from torchflows_amd.bijections.finite.autoregressive.transformers.combination.sigmoid import (
     DeepSigmoid)
+from torchflows_amd.bijections.finite.autoregressive.transformers.combination.dense_sigmoid import (
+    DeepDenseSigmoid, DenseSigmoid)
 from torchflows_amd.bijections.finite.autoregressive.transformers.spline.linear_rational import (
     LinearRational)
 from torchflows_amd.bijections.finite.autoregressive.transformers.spline.rational_quadratic import (
@@ -197,3 +199,40 @@ class DeepSigmoidalForwardMaskedAutoregressive(MaskedAutoregressiveBijection):
 
     def __init__(self, event_shape: Sequence[int], **kwargs):
         super().__init__(event_shape, DeepSigmoid, **kwargs)
+
+
+# -- dense sigmoidal layers (reference :202-295): 80 % of the transformer's parameters are learned constants unless the
+# conditioner keywords say otherwise.  (A MADE conditioner swallows the keyword: the MADE twins predict everything.)
+def _dense_defaults(kwargs: dict) -> dict:
+    kwargs.setdefault("conditioner_kwargs", {}).setdefault("percentage_global_parameters", 0.8)
+    return kwargs
+
+
+class DenseSigmoidalCoupling(CouplingBijection):
+    def __init__(self, event_shape: Sequence[int], **kwargs):
+        super().__init__(event_shape, DenseSigmoid, **_dense_defaults(kwargs))
+
+
+class DenseSigmoidalInverseMaskedAutoregressive(InverseMaskedAutoregressiveBijection):
+    def __init__(self, event_shape: Sequence[int], **kwargs):
+        super().__init__(event_shape, DenseSigmoid, **_dense_defaults(kwargs))
+
+
+class DenseSigmoidalForwardMaskedAutoregressive(MaskedAutoregressiveBijection):
+    def __init__(self, event_shape: Sequence[int], **kwargs):
+        super().__init__(event_shape, DenseSigmoid, **_dense_defaults(kwargs))
+
+
+class DeepDenseSigmoidalCoupling(CouplingBijection):
+    def __init__(self, event_shape: Sequence[int], **kwargs):
+        super().__init__(event_shape, DeepDenseSigmoid, **_dense_defaults(kwargs))
+
+
+class DeepDenseSigmoidalInverseMaskedAutoregressive(InverseMaskedAutoregressiveBijection):
+    def __init__(self, event_shape: Sequence[int], **kwargs):
+        super().__init__(event_shape, DeepDenseSigmoid, **_dense_defaults(kwargs))
+
+
+class DeepDenseSigmoidalForwardMaskedAutoregressive(MaskedAutoregressiveBijection):
+    def __init__(self, event_shape: Sequence[int], **kwargs):
+        super().__init__(event_shape, DeepDenseSigmoid, **_dense_defaults(kwargs))

@@ -32,6 +32,43 @@ from torchflows_amd.bijections.finite.autoregressive.transformers.base import (
 from torchflows_amd.utils import as_rows, get_batch_shape
 
 
+def _dense_inputs(layer, x_in: torch.Tensor, ctx, targets: torch.Tensor):
+    """What csrc/tfk_dense_dsf.hip takes in place of the parameter tensor of a dense sigmoidal layer: the conditioner's
+    predicted block as its last GEMM leaves it -- (N, n_predicted) of a coupling conditioner, the whole un-gathered
+    (N, D P) output of a MADE -- or None when nothing is predicted, and the descriptor block that says where each
+    parameter comes from (native.dense_descriptor).  The descriptor holds the learned constants: cached on the layer
+    until a tensor of the conditioner changes (fused._params_version; dropped with every other ``_tfk_`` cache)."""
+    from torchflows_amd import fused
+    ct = layer.conditioner_transform
+    made = isinstance(ct, MADE)
+    version = fused._params_version(ct)
+    hit = layer.__dict__.get("_tfk_dense_desc")
+    if hit is None or hit[0] != version:
+        theta = ct.global_theta_flat.detach()
+        n = ct.n_transformer_parameters
+        constant = torch.zeros(n, dtype=torch.bool, device=theta.device)
+        if ct.global_parameter_mask is not None:
+            constant = ct.global_parameter_mask.reshape(-1).to(theta.device)
+        base = torch.zeros(n, dtype=torch.float32, device=theta.device)
+        base[constant] = theta.float()
+        col = torch.arange(n, device=theta.device) if made else torch.cumsum(~constant, 0) - 1
+        col = torch.where(constant, torch.full_like(col, -1), col)
+        stride = n if made else ct.n_predicted_parameters
+        hit = (version, native.dense_descriptor(targets, stride, col, base))
+        layer.__dict__["_tfk_dense_desc"] = hit
+    if ct.n_predicted_parameters == 0:
+        return None, hit[1]
+    pred = ct.sequential(ct.context_combiner(x_in, ctx)) if made else ct.predict_theta_flat(x_in, ctx)
+    return pred.reshape(x_in.shape[0], -1).contiguous(), hit[1]
+
+
+def _dense_route_ok(layer) -> bool:
+    """The dense kernel composes raw parameters: a conditioner that squashes its output declines the route."""
+    ct = layer.conditioner_transform
+    return (layer.transformer.native_kind != "dense"
+            or (ct.output_lower_bound == float("-inf") and ct.output_upper_bound == float("inf")))
+
+
 class AutoregressiveBijection(Bijection):
     """conditioner_transform -> h, transformer(x, h) (reference :14-48)."""
 
@@ -139,7 +176,7 @@ class CouplingBijection(AutoregressiveBijection):
     # -- HIP path ------------------------------------------------------------------
     def _native_supported(self) -> bool:
         """Is there a libtfk kernel for this layer's transformer?"""
-        return native.coupling_kernel(self.transformer)
+        return native.coupling_kernel(self.transformer) and _dense_route_ok(self)
 
     def _native_ok(self, x, context) -> bool:
         return self._native_supported() and native.eligible(x, context) and _params_ok(self)
@@ -154,9 +191,12 @@ class CouplingBijection(AutoregressiveBijection):
         x_a = rows[:, :S] if self._source_is_head else rows.index_select(1, self._source_index)
         x_a = x_a.reshape(N, *self.coupling.constant_shape)
         ctx = None if context is None else context.reshape(N, *self.context_shape)
-        h = self.conditioner_transform(x_a, context=ctx).reshape(N, -1).contiguous()
-        out = rows if state.owned else state.out_buffer()
         tgt = None if self._target_is_tail else self._target_index32
+        if self.transformer.native_kind == "dense":      # (h: the predicted block, tgt: the descriptor -- never a tail)
+            h, tgt = _dense_inputs(self, x_a, ctx, self._target_index32)
+        else:
+            h = self.conditioner_transform(x_a, context=ctx).reshape(N, -1).contiguous()
+        out = rows if state.owned else state.out_buffer()
         native.transform(self.transformer, d == INVERSE, rows, h, out, state.logdet, tgt, T, state.started)
         state.started = True
         state.commit(out)
@@ -216,7 +256,7 @@ class MaskedAutoregressiveBijection(AutoregressiveBijection):
 
     # -- HIP path ----------------------------------------------------------------------
     def _native_supported(self) -> bool:
-        return native.made_kernel(self.transformer)
+        return native.made_kernel(self.transformer) and _dense_route_ok(self)
 
     def _native_ok(self, x, context) -> bool:
         return self._native_supported() and native.eligible(x, context) and _params_ok(self)
@@ -224,8 +264,13 @@ class MaskedAutoregressiveBijection(AutoregressiveBijection):
     def _native_pass(self, rows, out, logdet, context, transformer_inverse: bool, accumulate: bool):
         N, D = rows.shape
         ctx = None if context is None else context.reshape(N, *self.context_shape)
-        h = self.conditioner_transform(rows.view(N, *self.event_shape), ctx).reshape(N, -1).contiguous()
-        native.transform(self.transformer, transformer_inverse, rows, h, out, logdet, None, D, accumulate)
+        tgt = None
+        if self.transformer.native_kind == "dense":
+            h, tgt = _dense_inputs(self, rows.view(N, *self.event_shape), ctx,
+                                   torch.arange(D, dtype=torch.int32, device=rows.device))
+        else:
+            h = self.conditioner_transform(rows.view(N, *self.event_shape), ctx).reshape(N, -1).contiguous()
+        native.transform(self.transformer, transformer_inverse, rows, h, out, logdet, tgt, D, accumulate)
 
     def _made_pack(self):
         """(W1t, b1, W2, b2) for tfk_made_affine_sequential / tfk_made_rqs_sequential -- masked,

@@ -1,6 +1,7 @@
 // tfk_dsf.h -- the arithmetic of one deep sigmoidal component (transformers/combination/sigmoid.py), shared by the
 // coupling kernels that read their parameters from HBM (tfk_dsf.hip) and the image kernel that makes them on the matrix
-// cores (tfk_glow_dsf.hip).  Per element a component takes 3 K parameters [da (K) | db (K) | dw (K)]:
+// cores (tfk_glow_dsf.hip); below it the pieces of a coupling tile (target mask, per-row log-det, pass-through copy) that
+// tfk_dsf.hip shares with the dense sigmoidal kernel (tfk_dense_dsf.hip).  Per element a component takes 3 K parameters [da (K) | db (K) | dw (K)]:
 //     a = softplus(log(e - 1 - 1e-3) + da / 1000) + 1e-3,  b = db / 1000,  w = softmax(dw / 1000)
 //     d = clip(sum_j w_j sigmoid(a_j x + b_j), 1e-6, 1 - 1e-6),  z = log d - log1p(-d)      (1 - d: dsf_logit below)
 //     log-det (as the reference has it) = K (log d - log(1 - d)) + sum_j [log w_j + log a_j + log sigmoid(c_j) + log sigmoid(-c_j)]
@@ -145,5 +146,72 @@ __device__ __forceinline__ void dsf_step(const DsfComp<K> &q, float &v, float &t
         total -= l;
     }
 }
+
+// ---- a coupling tile: `block` lanes, one element each, R = block / T rows per tile (rows longer than a tile: in chunks) ----
+
+// is_tgt[c] = column c is transformed (the pass-through copy leaves it alone)
+__device__ __forceinline__ void dsf_mark_targets(unsigned char *is_tgt, const int *__restrict__ tgt_idx, int T, int D, int block)
+{
+    const int tid = threadIdx.x;
+    for (int e = tid; e < D; e += block) is_tgt[e] = 0;
+    __syncthreads();
+    for (int t = tid; t < T; t += block) is_tgt[tgt_idx[t]] = 1;
+}
+
+// Per-row log-det of a tile of whole rows: inside the T-lane group (T a power of two <= 64) or through ld_s (block floats).
+// `first`: this lane holds element 0 of a live row `row`.  Every lane of the workgroup calls it.
+__device__ __forceinline__ void dsf_row_logdet(float ld, float *ld_s, float *logdet, long long row0, long long row, int rows,
+                                               int T, bool first, bool shfl_reduce, int accumulate)
+{
+    const int tid = threadIdx.x;
+    if (shfl_reduce) {
+        const float sum = group_sum(ld, T);
+        if (first) logdet[row] = accumulate ? logdet[row] + sum : sum;
+    } else {
+        ld_s[tid] = ld;
+        __syncthreads();
+        if (tid < rows) {
+            float sum = 0.0f;
+            for (int jj = 0; jj < T; ++jj) sum += ld_s[tid * T + jj];
+            logdet[row0 + tid] = accumulate ? logdet[row0 + tid] + sum : sum;
+        }
+    }
+}
+
+// ... of ONE row longer than the tile: the lanes' sums over its chunks, added in a tree (block: a power of two)
+__device__ __forceinline__ void dsf_long_row_logdet(float ld_thread, float *ld_s, float *logdet, long long row0, int block,
+                                                    int accumulate)
+{
+    const int tid = threadIdx.x;
+    __syncthreads();
+    ld_s[tid] = ld_thread;
+    __syncthreads();
+    for (int o = block / 2; o > 0; o >>= 1) {
+        if (tid < o) ld_s[tid] += ld_s[tid + o];
+        __syncthreads();
+    }
+    if (tid == 0) logdet[row0] = accumulate ? logdet[row0] + ld_s[0] : ld_s[0];
+}
+
+// the columns that are no targets, copied (clone, layers_base.py); is_tgt: dsf_mark_targets, unused for a tail (no tgt_idx)
+__device__ __forceinline__ void dsf_copy_passthrough(const float *x, float *z, long long row0, int rows, int D, int T,
+                                                     const int *tgt_idx, const unsigned char *is_tgt, int block)
+{
+    const int total = rows * D;
+    for (int e = threadIdx.x; e < total; e += block) {
+        const int rr = e / D;
+        const int c = e - rr * D;
+        const bool tgt = tgt_idx ? (is_tgt[c] != 0) : (c >= D - T);
+        if (!tgt) z[(row0 + rr) * D + c] = x[(row0 + rr) * D + c];
+    }
+}
+
+// ---- the dense sigmoidal family (tfk_dense_dsf.hip) behind tfk_dsf_supported / tfk_dsf_coupling_fwd / _inv: n_components
+// carries C | (L + 1) << 8 (include/tfk.h) ----
+inline bool dsf_is_dense(int32_t n_components) { return (n_components >> 8) != 0; }
+bool dense_dsf_supported(int32_t n_components, int32_t hidden);
+int dense_dsf_coupling(bool inverse, const float *x, const float *pred, float *z, float *logdet, int64_t N, int32_t D,
+                       const int32_t *desc, int32_t T, int32_t n_components, int32_t hidden, int32_t accumulate,
+                       void *stream, const char *fn);
 
 }  // namespace tfk

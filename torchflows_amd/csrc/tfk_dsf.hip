@@ -50,11 +50,7 @@ __global__ __launch_bounds__(dsf_block(K)) void k_dsf_coupling(
     unsigned char *is_tgt = reinterpret_cast<unsigned char *>(ld_s + BLOCK);
     const int tid = threadIdx.x;
     const bool use_mask = (tgt_idx != nullptr) && !inplace;
-    if (use_mask) {
-        for (int e = tid; e < D; e += BLOCK) is_tgt[e] = 0;
-        __syncthreads();
-        for (int t = tid; t < T; t += BLOCK) is_tgt[tgt_idx[t]] = 1;
-    }
+    if (use_mask) dsf_mark_targets(is_tgt, tgt_idx, T, D, BLOCK);
     const int R = T <= BLOCK ? BLOCK / T : 1;
     const int chunks = T <= BLOCK ? 1 : (T + BLOCK - 1) / BLOCK;
     const long long n_tiles = (N + R - 1) / R;
@@ -95,40 +91,11 @@ __global__ __launch_bounds__(dsf_block(K)) void k_dsf_coupling(
                 dsf_eval<K, INVERSE>(rec + tid * PS, C, v, o, ld);
                 z[row * D + idx] = o;
             }
-            if (chunks > 1) {
-                ld_thread += ld;
-            } else if (shfl_reduce) {
-                const float sum = group_sum(ld, T);
-                if (tid < E && t == 0) logdet[row] = accumulate ? logdet[row] + sum : sum;
-            } else {
-                ld_s[tid] = ld;
-                __syncthreads();
-                if (tid < rows) {
-                    float sum = 0.0f;
-                    for (int jj = 0; jj < T; ++jj) sum += ld_s[tid * T + jj];
-                    logdet[row0 + tid] = accumulate ? logdet[row0 + tid] + sum : sum;
-                }
-            }
+            if (chunks > 1) ld_thread += ld;
+            else dsf_row_logdet(ld, ld_s, logdet, row0, row, rows, T, tid < E && t == 0, shfl_reduce, accumulate);
         }
-        if (chunks > 1) {
-            __syncthreads();
-            ld_s[tid] = ld_thread;
-            __syncthreads();
-            for (int o = BLOCK / 2; o > 0; o >>= 1) {
-                if (tid < o) ld_s[tid] += ld_s[tid + o];
-                __syncthreads();
-            }
-            if (tid == 0) logdet[row0] = accumulate ? logdet[row0] + ld_s[0] : ld_s[0];
-        }
-        if (!inplace) {                                            // clone, layers_base.py
-            const int total = rows * D;
-            for (int e = tid; e < total; e += BLOCK) {
-                const int rr = e / D;
-                const int c = e - rr * D;
-                const bool tgt = tgt_idx ? (is_tgt[c] != 0) : (c >= D - T);
-                if (!tgt) z[(row0 + rr) * D + c] = x[(row0 + rr) * D + c];
-            }
-        }
+        if (chunks > 1) dsf_long_row_logdet(ld_thread, ld_s, logdet, row0, BLOCK, accumulate);
+        if (!inplace) dsf_copy_passthrough(x, z, row0, rows, D, T, tgt_idx, is_tgt, BLOCK);
     }
 }
 
@@ -309,6 +276,7 @@ extern "C" {
 
 int tfk_dsf_supported(int32_t n_components, int32_t hidden_dim)
 {
+    if (tfk::dsf_is_dense(n_components)) return tfk::dense_dsf_supported(n_components, hidden_dim) ? 1 : 0;
     return tfk::dsf_supported(n_components, hidden_dim) ? 1 : 0;
 }
 
@@ -316,6 +284,9 @@ int tfk_dsf_coupling_fwd(const float *x, const float *h, float *z, float *logdet
                          const int32_t *tgt_idx, int32_t T, int32_t n_components, int32_t hidden_dim,
                          int32_t accumulate, void *stream)
 {
+    if (tfk::dsf_is_dense(n_components))
+        return tfk::dense_dsf_coupling(false, x, h, z, logdet, N, D, tgt_idx, T, n_components, hidden_dim, accumulate, stream,
+                                       "tfk_dsf_coupling_fwd");
     return tfk::dsf_coupling<false>(x, h, z, logdet, N, D, tgt_idx, T, n_components, hidden_dim, accumulate, stream,
                                     "tfk_dsf_coupling_fwd");
 }
@@ -324,6 +295,9 @@ int tfk_dsf_coupling_inv(const float *z, const float *h, float *x, float *logdet
                          const int32_t *tgt_idx, int32_t T, int32_t n_components, int32_t hidden_dim,
                          int32_t accumulate, void *stream)
 {
+    if (tfk::dsf_is_dense(n_components))
+        return tfk::dense_dsf_coupling(true, z, h, x, logdet, N, D, tgt_idx, T, n_components, hidden_dim, accumulate, stream,
+                                       "tfk_dsf_coupling_inv");
     return tfk::dsf_coupling<true>(z, h, x, logdet, N, D, tgt_idx, T, n_components, hidden_dim, accumulate, stream,
                                    "tfk_dsf_coupling_inv");
 }
@@ -335,6 +309,9 @@ int tfk_dsf_coupling_bwd(const float *x, const float *h, float *g, const float *
     using namespace tfk;
     const char *fn = "tfk_dsf_coupling_bwd";
     const int C = n_components, K = hidden_dim;
+    if (dsf_is_dense(n_components))
+        return fail(TFK_EINVAL, "%s: the dense sigmoidal family has no reverse-mode kernel; differentiate it on the ATen "
+                    "path", fn);
     if (const int rc = dsf_check(fn, N, D, T, C, K)) return rc;
     if (inverse)
         return fail(TFK_EINVAL, "%s: the inverse direction is a bisection without gradient; differentiate it on the ATen "

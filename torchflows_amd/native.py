@@ -373,6 +373,42 @@ def dsf_coupling(x, h, out, logdet, tgt_idx, T, n_components, hidden_dim, accumu
               extra=(int(n_components), int(hidden_dim)))
 
 
+def dense_code(n_components, n_dense_layers) -> int:
+    """What the dense sigmoidal family passes as ``n_components``: C | (L + 1) << 8 (include/tfk.h)."""
+    return int(n_components) | ((int(n_dense_layers) + 1) << 8)
+
+
+def dense_descriptor(targets, stride, col, base) -> torch.Tensor:
+    """The int32 block ``[T target columns | stride | col (T P) | base (T P, float bits)]`` the dense family takes in
+    ``tgt_idx``: entry j of target t is ``pred[n, col[t P + j]]`` where ``col >= 0`` and the constant ``base[t P + j]``
+    otherwise.  Checked here, on the host: the kernel trusts it."""
+    T = targets.numel()
+    if col.numel() != base.numel() or col.numel() % T:
+        raise NativeError(f"dense_descriptor: col has {col.numel()} entries, base {base.numel()}, for T = {T} targets")
+    if int(col.max()) >= int(stride) or int(col.min()) < -1 or int(targets.min()) < 0:
+        raise NativeError(f"dense_descriptor: a column outside [-1, stride = {int(stride)}) or a negative target")
+    head = torch.tensor([int(stride)], dtype=torch.int32, device=base.device)
+    return torch.cat([targets.to(base.device, torch.int32).reshape(-1), head, col.to(base.device, torch.int32).reshape(-1),
+                      base.to(torch.float32).reshape(-1).view(torch.int32)])
+
+
+def dense_coupling(x, pred, out, logdet, desc, T, n_components, n_dense_layers, hidden_size, accumulate=False,
+                   inverse=False):
+    """Dense sigmoidal coupling (csrc/tfk_dense_dsf.hip) on the T target columns of x (N, D).  pred: the conditioner's
+    predicted block (N, stride), or None when every parameter is a learned constant; desc: ``dense_descriptor``.
+    ``inverse``: the whole bisection in the launch."""
+    name = "tfk_dsf_coupling_inv" if inverse else "tfk_dsf_coupling_fwd"
+    N, D = _rows(x, name)
+    P = (desc.numel() - T - 1) // (2 * T)
+    if out.shape != x.shape or logdet.numel() != N or desc.numel() != T + 1 + 2 * T * P or int(T) > D:
+        raise NativeError(f"{name}: out {tuple(out.shape)}, logdet {logdet.numel()}, descriptor {desc.numel()} do not fit "
+                          f"x {tuple(x.shape)} with T = {T}")
+    if pred is not None and (pred.dim() != 2 or pred.shape[0] != N):
+        raise NativeError(f"{name}: the predicted block has shape {tuple(pred.shape)}, expected ({N}, stride)")
+    _launch(name, x, _f32(x, name), _f32(pred, name), _f32(out, name), _f32(logdet, name), N, D, _idx(desc, name), T,
+            dense_code(n_components, n_dense_layers), int(hidden_size), 1 if accumulate else 0)
+
+
 def conv1x1_coupling(x, h, out, logdet, tgt_idx, T, n_channels, accumulate=False, inverse=False):
     """Invertible 1x1 convolution on the T target positions (n_channels x T/n_channels pixels,
     channel-major); h: (N, n + n(n-1)) LU parameters per sample."""
@@ -480,6 +516,16 @@ def _dsf_native(tr) -> bool:
     return dsf_supported(tr.n_components, tr.hidden_dim)
 
 
+def _dense_native(tr) -> bool:
+    """A dense sigmoidal transformer of a size csrc/tfk_dense_dsf.hip serves (tfk_dsf_supported with the family's code in
+    n_components: an older library answers 0); TORCHFLOWS_AMD_DEBUG="dense=0" forces the ATen composite path (A/B runs,
+    tools/dense_rows.py)."""
+    from torchflows_amd.utils import debug_switch
+    if debug_switch("dense", "1") == "0":
+        return False
+    return dsf_supported(dense_code(tr.n_components, tr.n_dense_layers), tr.hidden_size)
+
+
 def _always(tr) -> bool:
     return True
 
@@ -516,6 +562,9 @@ KINDS = {
     "lrs": TransformerKind("lrs_coupling", "lrs_coupling_bwd", attrgetter("n_bins", "boundary"), False, _lrs_bins, _lrs_bins, _lrs_bins),
     "dsf": TransformerKind("dsf_coupling", "dsf_coupling_bwd", attrgetter("n_components", "hidden_dim"), False,
                            _dsf_native, _dsf_native, _dsf_native),
+    # (h: the conditioner's predicted block, tgt: the layer's descriptor block -- layers_base.py: _dense_inputs)
+    "dense": TransformerKind("dense_coupling", "", attrgetter("n_components", "n_dense_layers", "hidden_size"), False,
+                             _dense_native, _dense_native, _never),
     "conv1x1": TransformerKind("conv1x1_coupling", "conv1x1_coupling_bwd", lambda tr: (tr.n_channels,), False,
                                lambda tr: tr.n_channels <= 16,      # channels are kept in registers
                                _never, lambda tr: int(tr.n_channels) <= 16),
