@@ -425,7 +425,19 @@ int tfk_lrs_coupling_inv(const float *z, const float *h, float *x, float *logdet
  *           The kernel does not check it: targets in [0, D), col in [-1, stride).
  *   Supported (tfk_dsf_supported; anything else is TFK_EINVAL): 1 <= H <= 8, 0 <= L <= 2, C = 1 or 2, C P <= 512.  A
  *   library without the family answers 0 (C = 0 components there), which is the probe.
- *   inv: the same bisection, once per component (last to first) over its L + 2 transforms.  bwd: TFK_EINVAL. */
+ *   inv: the same bisection, once per component (last to first) over its L + 2 transforms.
+ *   bwd: reverse mode of fwd, recomputed from x, h (the predicted block or NULL) and the descriptor block; in place on g at
+ *   the target columns; inverse != 0 is TFK_EINVAL as above.  gh is ONE caller-owned block of floats, sized from this
+ *   comment alone (stride: the descriptor's; 0 floats of the last part when h is NULL):
+ *       [dL/dbase (T C P) | workspace (256 x T C P) | dL/dpred (N x stride)]
+ *   dL/dpred[n, col[t C P + j]] is the gradient of raw parameter j of target t for every (t, j) with col >= 0.  The
+ *   descriptor must name every predicted column AT MOST ONCE: the kernel relies on it (plain stores, no atomics).  Columns
+ *   no (t, j) names are NOT written: the caller zero-fills dL/dpred before the call.  dL/dbase[t C P + j] is the sum over
+ *   the N rows for col < 0 and 0 elsewhere; it is summed in a fixed order through the workspace (one slice per workgroup,
+ *   at most 256 of them, added in slice order by a second kernel): two calls on the same inputs give the same bits.
+ *   N = 0 returns TFK_OK before any pointer is looked at and writes nothing.  A library without the kernel answers
+ *   TFK_EINVAL to that call, which is the probe (N = 0, D = T = 1, n_components = 1 | 1 << 8, hidden_dim = 1, null
+ *   pointers): it needs no device. */
 int tfk_dsf_supported(int32_t n_components, int32_t hidden_dim);
 int tfk_dsf_coupling_fwd(const float *x, const float *h, float *z, float *logdet, int64_t N, int32_t D,
                          const int32_t *tgt_idx, int32_t T, int32_t n_components, int32_t hidden_dim,

@@ -9,7 +9,12 @@ One JSON line per measurement:
   * ``tfk_dsf_coupling_fwd`` / ``_inv`` of the first coupling alone, on its own conditioner's predicted block: us per
     launch; for fwd the HBM floor (N n_predicted + 2 N D + N) * 4 bytes over ``--stream-tbs`` (default 5.5 TB/s); for inv
     the mean bisection trips per component, counted by re-enacting the kernel's rule with ATen ops on the first 512 rows;
-  * ``log_prob`` and ``sample`` of the whole flow, route ``dense=1`` and ``dense=0``.
+  * ``log_prob`` and ``sample`` of the whole flow, route ``dense=1`` and ``dense=0``;
+  * the training leg (``--train-rows``, default 2^12: the ATen graph keeps the composed (N, 32, 243 / 486) tensor of every
+    layer): ``tfk_dsf_coupling_bwd`` of the first coupling alone (its gradient rows restored by a copy inside the timed
+    call), then one maximum-likelihood step ``log_prob(x).mean().backward()`` on the reverse-mode kernel against
+    ``dense_train=0`` (this build's ATen graph), alternating, with the peak allocated memory of a step of each.
+``--legs eval`` / ``--legs train`` runs one of the two halves.
 """
 import argparse
 import json
@@ -29,6 +34,55 @@ from tools.dsf_rows import report, timed  # noqa: E402
 
 def set_route(on: bool):
     os.environ["TORCHFLOWS_AMD_DEBUG"] = "dense=1" if on else "dense=0"
+
+
+def stats(us):
+    return dict(us_per_call=round(statistics.median(us), 1), us_min=round(min(us), 1),
+                us_p90=round(sorted(us)[int(0.9 * len(us))], 1))
+
+
+def train_leg(args, flow, name, layer):
+    """The reverse-mode launch of ``layer`` alone, then a maximum-likelihood step of ``flow`` on both routes."""
+    from torchflows_amd import native
+    from torchflows_amd.bijections.finite.autoregressive.layers_base import _dense_inputs
+    N, D = args.train_rows, 64
+    x = torch.randn(N, D, device="cuda")
+    tr, T, S = layer.transformer, layer.coupling.target_event_size, layer.coupling.source_event_size
+    C, L, H = tr.n_components, tr.n_dense_layers, tr.hidden_size
+    set_route(True)
+    with torch.no_grad():
+        pred, desc = _dense_inputs(layer, x[:, :S].contiguous(), None, layer._target_index32)
+        g0, g, gld = torch.randn_like(x), torch.empty_like(x), torch.randn(N, device="cuda")
+        gh = torch.zeros(sum(native.dense_bwd_floats(N, T, tr.n_parameters_per_element, pred.shape[1])), device="cuda")
+        s = stats(timed(lambda: (g.copy_(g0), native.dense_coupling_bwd(x, pred, g, gld, gh, desc, T, C, L, H)), args.reps))
+        report(tag=args.tag, model=name, call="tfk_dsf_coupling_bwd", rows=N, T=T, n_predicted=pred.shape[1], **s)
+    del gh, pred
+
+    def step():
+        flow.zero_grad(set_to_none=True)
+        flow.log_prob(x).mean().backward()
+    specs = {"dense_train=1": "dense=1,dense_train=1", "dense_train=0": "dense=1,dense_train=0"}
+    us, extra = {}, {}
+    for route, spec in specs.items():                            # warm-up of both routes, launches and peak memory of a step
+        os.environ["TORCHFLOWS_AMD_DEBUG"] = spec
+        step()
+        step()
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        before = native.calls
+        step()
+        torch.cuda.synchronize()
+        extra[route] = dict(libtfk_launches=native.calls - before,
+                            peak_allocated_mib=round(torch.cuda.max_memory_allocated() / 2 ** 20, 1))
+        us[route] = []
+    for _ in range(args.train_reps):                             # alternating: one timed step each
+        for route, spec in specs.items():
+            os.environ["TORCHFLOWS_AMD_DEBUG"] = spec
+            us[route] += timed(step, 1, warmup=0)
+    for route in specs:
+        report(tag=args.tag, model=name, call="log_prob(x).mean().backward()", route=route, rows=N, **extra[route],
+               **stats(us[route]))
+    flow.zero_grad(set_to_none=True)
 
 
 def trip_counts(tr, z, h, max_trips=64):
@@ -60,6 +114,9 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--stream-tbs", type=float, default=5.5)
     ap.add_argument("--tag", default="")
+    ap.add_argument("--train-rows", type=int, default=1 << 12)
+    ap.add_argument("--train-reps", type=int, default=10)
+    ap.add_argument("--legs", default="eval,train")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/dense_rows.py needs a GPU")
@@ -68,10 +125,6 @@ def main():
     from torchflows_amd.bijections.finite.autoregressive.layers_base import _dense_inputs
     warnings.simplefilter("ignore")
     N, D = args.rows, 64
-
-    def stats(us):
-        return dict(us_per_call=round(statistics.median(us), 1), us_min=round(min(us), 1),
-                    us_p90=round(sorted(us)[int(0.9 * len(us))], 1))
 
     for ctor in (tfa.CouplingDenseSF, tfa.CouplingDeepDenseSF):
         name = f"{ctor.__name__}(64, n_layers=8)"
@@ -83,8 +136,12 @@ def main():
         flow = flow.eval().cuda()
         x = torch.randn(N, D, device="cuda")
         set_route(True)
+        layer = next(l for l in flow.bijection.layers if hasattr(l, "coupling"))
+        if "train" in args.legs:
+            train_leg(args, flow, name, layer)
+        if "eval" not in args.legs:
+            continue
         with torch.no_grad():
-            layer = next(l for l in flow.bijection.layers if hasattr(l, "coupling"))
             tr, T, S = layer.transformer, layer.coupling.target_event_size, layer.coupling.source_event_size
             C, L, H = tr.n_components, tr.n_dense_layers, tr.hidden_size
             pred, desc = _dense_inputs(layer, x[:, :S].contiguous(), None, layer._target_index32)

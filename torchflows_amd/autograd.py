@@ -22,6 +22,11 @@ the step.  The pack classes live in train_packs.py.  ``_PlanPacks`` resolves eve
 Only what the kernels cover takes this route (affine / inverse-affine / shift / RQ-spline
 couplings with 4, 8 or 16 bins, ElementwiseAffine / ActNorm, permutations, no context);
 anything else keeps the ATen composite graph.  ``TORCHFLOWS_AMD_TRAIN=0`` forces the latter.
+
+The dense sigmoidal layers (csrc/tfk_dense_dsf.hip) are layer-by-layer steps of their own shape: their kernels take the
+conditioner's predicted block and a descriptor instead of ``h``, so the forward step keeps that block with its graph and the
+backward step feeds the kernel's dL/dpred through it and scatters the batch-summed dL/dbase onto ``global_theta_flat``
+(``_dense_forward`` / ``_dense_backward``); forward direction only, the inverse is a bisection without gradient.
 """
 from __future__ import annotations
 
@@ -71,7 +76,7 @@ def live_forced() -> bool:
 
 def _step_kind(layer) -> Optional[str]:
     from torchflows_amd.bijections.finite.autoregressive.layers_base import (
-        CouplingBijection, ElementwiseBijection, MaskedAutoregressiveBijection)
+        CouplingBijection, ElementwiseBijection, MaskedAutoregressiveBijection, _dense_route_ok)
     from torchflows_amd.bijections.finite.matrix.permutation import PermutationMatrix
     if isinstance(layer, PermutationMatrix):
         return "perm"
@@ -79,7 +84,7 @@ def _step_kind(layer) -> Optional[str]:
         # the parallel pass (MAF density / IAF sampling): MADE on PyTorch-ROCm, the transformer's
         # forward and reverse-mode kernels with every position a target
         tr = layer.transformer
-        ok = layer.context_shape is None and native.made_kernel(tr) and native.reverse_kernel(tr)
+        ok = layer.context_shape is None and native.made_kernel(tr) and native.reverse_kernel(tr) and _dense_route_ok(layer)
         return "made" if ok else None
     if isinstance(layer, ElementwiseBijection):
         if layer.transformer.native_kind not in ("affine", "inverse_affine"):
@@ -89,7 +94,7 @@ def _step_kind(layer) -> Optional[str]:
         return "elementwise" if layer.use_global_parameters else "elementwise_ctx"
     if isinstance(layer, CouplingBijection):
         # (a context only enters the conditioner, by concatenation: conditioning/context.py:38-64)
-        if native.reverse_kernel(layer.transformer):
+        if native.reverse_kernel(layer.transformer) and _dense_route_ok(layer):
             return "coupling"
     return None
 
@@ -100,7 +105,8 @@ def training_plan(composition, direction: int):
     # by the identity of its layers (dropped with every other ``_tfk_`` cache on train() / eval() / load_state_dict /
     # a move); 27 layers x isinstance chains cost 60 us of a 1.5 ms step
     from torchflows_amd import fused
-    key = (fused._EPOCH[0], tuple(map(id, composition.layers)))
+    # (... and the debug switches: dsf / dense / dense_train decide whether a kind has reverse-mode kernels)
+    key = (fused._EPOCH[0], tuple(map(id, composition.layers)), os.environ.get("TORCHFLOWS_AMD_DEBUG", ""))
     cache = composition.__dict__.setdefault("_tfk_train_plan", {})
     hit = cache.get(direction)
     if hit is not None and hit[0] == key:
@@ -115,7 +121,7 @@ def training_plan(composition, direction: int):
             if kind is None or (kind == "made" and d == layer._sequential_when):
                 steps = None    # (the element-by-element map is not differentiated on the HIP path)
                 break
-            if kind == "coupling" and d == INVERSE and layer.transformer.native_kind == "dsf":
+            if kind == "coupling" and d == INVERSE and layer.transformer.native_kind in ("dsf", "dense"):
                 steps = None    # (a bisection without gradient: the ATen graph, as the reference differentiates it)
                 break
             steps.append((layer, d, kind))
@@ -946,7 +952,59 @@ def _bwd_elementwise_ctx(st, i, layer, d):
     st.grads_per_step[i] = _graph_param_grads(_graph_grads(h2, [], gh, cparams)[1], cparams, zeros=True)
 
 
+def _is_dense(layer) -> bool:
+    return layer.transformer.native_kind == "dense"
+
+
+def _dense_forward(st, step, layer, x_in, targets, T: int) -> None:
+    """A dense sigmoidal layer (csrc/tfk_dense_dsf.hip): the conditioner's predicted block and the layer's descriptor in
+    place of h (layers_base.py: _dense_inputs).  The predicted block is kept WITH its graph for the backward pass, as a
+    convolutional conditioner's output is; ``x_in``: the conditioner's input, ``targets``: the int32 target columns."""
+    from torchflows_amd.bijections.finite.autoregressive.layers_base import _dense_inputs
+    ctx = _layer_context(layer, st.plan.context)
+    if st.keep_graphs:
+        x_in = x_in.detach().requires_grad_(True)
+        with torch.enable_grad():
+            pred, desc = _dense_inputs(layer, x_in, ctx, targets)
+        st.kept[step] = x_in, pred, desc
+        pred = None if pred is None else pred.detach()
+    else:
+        pred, desc = _dense_inputs(layer, x_in, ctx, targets)
+    st.transform(layer, FORWARD, pred, desc, T)
+
+
+def _dense_backward(st, i, layer, T: int):
+    """Reverse mode of ``_dense_forward``: one launch gives dL/dx at the targets (in place on ``st.g``), dL/dpred and the
+    batch-summed dL/dbase.  dL/dpred goes through the kept graph of the conditioner (its weights, its input); dL/dbase is
+    scattered onto ``global_theta_flat`` through ``global_parameter_mask`` -- the inverse of _dense_inputs' gather.
+    Returns dL/d(conditioner input) (None: nothing is predicted); the parameter gradients go to ``st.grads_per_step``."""
+    x_in, pred, desc = st.kept[i]
+    st.kept[i] = None
+    ct = layer.conditioner_transform
+    cparams = _module_params(ct)
+    dpred, dbase = native.transform_bwd(layer.transformer, False, st.saved[i], None if pred is None else pred.detach(),
+                                        st.g, st.gld, None, desc, T)
+    g_in, grads = None, [None] * len(cparams)
+    if pred is not None:
+        (g_in,), outs = _graph_grads(pred, [x_in], dpred, cparams)
+        grads = _graph_param_grads(outs, cparams, zeros=False)
+    theta = ct.global_theta_flat
+    if theta.requires_grad and theta.numel():
+        index = layer.__dict__.get("_tfk_dense_theta_index")
+        if index is None or index.device != dbase.device:
+            index = torch.nonzero(ct.global_parameter_mask.reshape(-1)).reshape(-1).to(dbase.device)
+            layer.__dict__["_tfk_dense_theta_index"] = index
+        k = next(n for n, p in enumerate(cparams) if p is theta)
+        g_theta = dbase.index_select(0, index).to(theta.dtype)
+        grads[k] = g_theta if grads[k] is None else grads[k] + g_theta
+    st.grads_per_step[i] = grads
+    return g_in
+
+
 def _fwd_made(st, step, layer, d):
+    if _is_dense(layer):
+        every = torch.arange(st.D, dtype=torch.int32, device=st.device)
+        return _dense_forward(st, step, layer, st.cur.view(st.N, *layer.event_shape), every, st.D)
     h = layer.conditioner_transform(st.cur.view(st.N, *layer.event_shape), None).reshape(st.N, -1).contiguous()
     st.transform(layer, FORWARD, h, None, st.D)
 
@@ -954,6 +1012,11 @@ def _fwd_made(st, step, layer, d):
 def _bwd_made(st, i, layer, d):
     # h depends on every input position (through the masks): re-evaluate MADE with a graph,
     # the transformer's reverse-mode kernel gives dL/dh and the direct dL/dx, autograd the rest
+    if _is_dense(layer):
+        g_in = _dense_backward(st, i, layer, st.D)
+        if g_in is not None:
+            st.g.add_(g_in.reshape(st.N, st.D))
+        return
     x_in, g, N = st.saved[i], st.g, st.N
     cparams = _module_params(layer.conditioner_transform)
     mlp = _made_mlp(layer)
@@ -1074,6 +1137,9 @@ def _bwd_rqs(st, i, layer, d):               # conditioner re-evaluated in the k
 
 def _fwd_layerwise(st, step, layer, d):
     x_a = _source_rows(layer, st.cur)
+    if _is_dense(layer):                    # (forward direction only: training_plan)
+        return _dense_forward(st, step, layer, x_a.reshape(st.N, *layer.coupling.constant_shape), layer._target_index32,
+                              layer.coupling.target_event_size)
     if _keeps_graph(layer) and st.keep_graphs:
         # a convolutional conditioner: evaluated ONCE, with its graph (the activations it saves are what a
         # re-evaluation in the backward pass would produce again -- and a BatchNorm in training mode counts
@@ -1091,6 +1157,14 @@ def _fwd_layerwise(st, step, layer, d):
 def _bwd_layerwise(st, i, layer, d):
     x_in, g, N = st.saved[i], st.g, st.N
     S = layer.coupling.source_event_size
+    if _is_dense(layer):
+        g_xa = _dense_backward(st, i, layer, layer.coupling.target_event_size)
+        if g_xa is not None:
+            if layer._source_is_head:
+                g[:, :S].add_(g_xa.reshape(N, S))
+            else:
+                g.index_add_(1, layer._source_index, g_xa.reshape(N, S))
+        return
     tgt = None if layer._target_is_tail else layer._target_index32
     cparams = _module_params(layer.conditioner_transform)
     x_a = _source_rows(layer, x_in)

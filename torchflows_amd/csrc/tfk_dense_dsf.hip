@@ -356,4 +356,323 @@ int dense_dsf_coupling(bool inverse, const float *x, const float *pred, float *z
                    : dense_launch<false>(x, pred, z, logdet, N, D, desc, T, C, L, hidden, accumulate, stream, fn);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Reverse mode of the forward map, recomputed from x, the predicted block and the descriptor (what torch.autograd derives
+// from dense_sigmoid.py).  For one inner transform (i inputs v, o outputs), A_p = dL/dv'_p, B = dL/dlog-det:
+//     G_p     = dL/dD0_p = (A_p + i o B) / (d_p (1 - d_p)) inside the clip, 0 where it is active (ATen's clamp)
+//     dL/dc_j = (sum_p G_p w_pj) s_j (1 - s_j) + i o B (1 - 2 s_j)
+//     dL/da_j = dL/dc_j (u_j . v) + i o B / a_j       dL/db_j = dL/dc_j
+//     dL/dwp_pj = w_pj G_p (s_j - D0_p) + i B (1 - o w_pj)                                  (softmax and log_softmax of row p)
+//     dL/du_jk = dL/dc_j a_j v_k + o^2 B / sum_l u_lk;   dL/dup_jk = u_jk (dL/du_jk - sum_m dL/du_jm u_jm)    (i > 1)
+//     dL/dv_k = sum_j dL/dc_j a_j u_jk
+// and raw parameters are the pre-activations x 1000: da gains softplus' = 1 - exp(-(a - 1e-3)), everything 1 / 1000.
+// 1 - d, 1 - s and s_j - D0_p above one half come from the complements, as in dsf_bwd_comp (tfk_dsf.hip).
+//   * the forward kernel's layout: one lane = one element, its record of C P floats in the LDS at an odd stride, extracted
+//     in place; a component's L + 1 hidden activations are recomputed once into registers, then its transforms are walked
+//     last to first and the gradient of every raw parameter OVERWRITES the extracted one it belongs to (a softmax row's
+//     backward needs the row and its gradient only);
+//   * dL/dpred: the record floats with col >= 0 go back the way they came, plain stores -- the descriptor names every
+//     predicted column at most once (layers_base.py: _dense_inputs).  Columns it does not name are NOT written: the
+//     caller zero-fills dL/dpred (native.dense_coupling_bwd);
+//   * dL/dbase: the tile's records still lie in the LDS; lane i sums entries dj = i (mod block) over the tile's rows in row
+//     order and adds the sum to slice blockIdx.x of the workspace, tile after tile (a persistent workgroup; the same
+//     lane owns dj throughout, so the slice needs no synchronisation).  k_dense_bwd_sum then adds the slices in slice
+//     order: no atomics, two calls give the same bits.
+// ---------------------------------------------------------------------------------------------
+template <int I, int O>
+__device__ __forceinline__ void dense_inner_bwd(float *q, const float *vin, const float *A, float B, float *gv)
+{
+    constexpr float IO = (float)(I * O);
+    constexpr int W0 = 2 * O, U0 = 2 * O + O * O;
+    float s[O], t[O], ux[O], gs[O];
+#pragma unroll
+    for (int j = 0; j < O; ++j) {
+        float u = vin[0];
+        if (I > 1) {
+            u = 0.0f;
+#pragma unroll
+            for (int k = 0; k < I; ++k) u += q[U0 + j * I + k] * vin[k];
+        }
+        ux[j] = u;
+        const float c = q[j] * u + q[O + j];
+        const float e = exp_noovf(-__builtin_fabsf(c));
+        const float r = 1.0f / (1.0f + e);
+        const float er = e * r;
+        s[j] = c >= 0.0f ? r : er;
+        t[j] = c >= 0.0f ? er : r;
+        gs[j] = 0.0f;
+    }
+#pragma unroll
+    for (int p = 0; p < O; ++p) {
+        float d0 = s[0], cd = t[0];
+        if (O > 1) {
+            d0 = 0.0f;
+            cd = 0.0f;
+#pragma unroll
+            for (int j = 0; j < O; ++j) {
+                const float w = q[W0 + p * O + j];
+                d0 += w * s[j];
+                cd += w * t[j];
+            }
+        }
+        const float d = fminf(fmaxf(d0, kDsfEps), kDsfOneMinusEps);
+        const bool inside = (d0 >= kDsfEps) && (d0 <= kDsfOneMinusEps);      // clamp passes the gradient on its bounds
+        const float G = inside ? (A[p] + IO * B) / (d * dsf_complement(cd)) : 0.0f;
+        if (O > 1) {
+            const bool high = d0 > 0.5f;
+#pragma unroll
+            for (int j = 0; j < O; ++j) {
+                const float w = q[W0 + p * O + j];
+                gs[j] += G * w;
+                q[W0 + p * O + j] = (w * (G * (high ? cd - t[j] : s[j] - d0)) + B * ((float)I * (1.0f - (float)O * w))) / 1000.0f;
+            }
+        } else {
+            gs[0] += G;
+            q[W0] = 0.0f;                                           // (a 1 x 1 softmax is constant)
+        }
+    }
+    float colsum[I];                                               // sum_l u_lk, then o^2 B over it
+#pragma unroll
+    for (int k = 0; k < I; ++k) {
+        colsum[k] = 0.0f;
+        gv[k] = 0.0f;
+    }
+    if (I > 1) {
+#pragma unroll
+        for (int j = 0; j < O; ++j) {
+#pragma unroll
+            for (int k = 0; k < I; ++k) colsum[k] += q[U0 + j * I + k];
+        }
+#pragma unroll
+        for (int k = 0; k < I; ++k) colsum[k] = B * (float)(O * O) / fmaxf(colsum[k], 1.17549435e-38f);
+    }
+#pragma unroll
+    for (int j = 0; j < O; ++j) {
+        const float g_c = gs[j] * (s[j] * t[j]) + IO * B * (t[j] - s[j]);
+        const float a = q[j];
+        const float g_ux = g_c * a;
+        const float sp = 1.0f - exp_noovf(kDsfMinScale - a);        // softplus' = sigmoid = 1 - exp(-softplus)
+        q[j] = (g_c * ux[j] + IO * B / a) * sp / 1000.0f;
+        q[O + j] = g_c / 1000.0f;
+        if (I == 1) {
+            gv[0] += g_ux;
+            q[U0 + j] = 0.0f;                                       // (u = 1 whatever du holds)
+        } else {
+            float gu[I];
+            float dot = 0.0f;
+#pragma unroll
+            for (int k = 0; k < I; ++k) {
+                const float u = q[U0 + j * I + k];
+                gu[k] = g_ux * vin[k] + colsum[k];
+                dot += gu[k] * u;
+                gv[k] += g_ux * u;
+            }
+#pragma unroll
+            for (int k = 0; k < I; ++k) q[U0 + j * I + k] = q[U0 + j * I + k] * (gu[k] - dot) / 1000.0f;
+        }
+    }
+}
+
+// One extracted component at x: its record becomes the raw parameters' gradients; returns dL/dx.
+template <int H>
+__device__ __forceinline__ float dense_comp_bwd(float *q, int L, float x, float A, float B)
+{
+    float *q1 = q + dense_p_first(H), *q2 = q1 + dense_p_mid(H), *qlast = q1 + L * dense_p_mid(H);
+    float act[3][H];                                               // what the first L + 1 transforms give
+#pragma unroll
+    for (int j = 0; j < H; ++j) act[1][j] = act[2][j] = 0.0f;
+    float unused = 0.0f;
+    dense_inner<1, H, false, false>(q, &x, act[0], unused);
+    if (L > 0) dense_inner<H, H, false, false>(q1, act[0], act[1], unused);
+    if (L > 1) dense_inner<H, H, false, false>(q2, act[1], act[2], unused);
+    float last[H], gv[H], gw[H];
+#pragma unroll
+    for (int j = 0; j < H; ++j) last[j] = L == 0 ? act[0][j] : (L == 1 ? act[1][j] : act[2][j]);
+    dense_inner_bwd<H, 1>(qlast, last, &A, B, gv);
+    if (L > 1) {
+        dense_inner_bwd<H, H>(q2, act[1], gv, B, gw);
+#pragma unroll
+        for (int j = 0; j < H; ++j) gv[j] = gw[j];
+    }
+    if (L > 0) {
+        dense_inner_bwd<H, H>(q1, act[0], gv, B, gw);
+#pragma unroll
+        for (int j = 0; j < H; ++j) gv[j] = gw[j];
+    }
+    float gx;
+    dense_inner_bwd<1, H>(q, &x, gv, B, &gx);
+    return gx;
+}
+
+// ws: gridDim.x slices of T CP floats.  Dynamic LDS: block records x PS floats.
+template <int H>
+__global__ __launch_bounds__(256) void k_dense_dsf_coupling_bwd(
+    const float *__restrict__ x, const float *__restrict__ pred, float *g, const float *__restrict__ gld,
+    float *__restrict__ dpred, float *__restrict__ ws, long long N, int D, const int *__restrict__ desc, int T, int T_shift,
+    int C, int L, int P, int PS)
+{
+    const int block = blockDim.x;
+    const int CP = C * P;
+    extern __shared__ __attribute__((aligned(16))) float rec[];
+    const int *tgt_idx = desc;
+    const long long stride = desc[T];
+    const int *col = desc + T + 1;
+    const float *base = reinterpret_cast<const float *>(col + (long long)T * CP);
+    const int tid = threadIdx.x;
+    const long long TCP = (long long)T * CP;
+    float *slice = ws + blockIdx.x * TCP;
+    for (long long i = tid; i < TCP; i += block) slice[i] = 0.0f;  // (entry dj belongs to lane dj % block, here and below)
+    const int R = T <= block ? block / T : 1;
+    const int chunks = T <= block ? 1 : (T + block - 1) / block;
+    const long long n_tiles = (N + R - 1) / R;
+    const int r_first = tid / CP, j_first = tid - r_first * CP;
+    const int r_step = block / CP, j_step = block - r_step * CP;
+    const int rr_first = r_first / T, t_first = r_first - rr_first * T;
+    const int rr_step = r_step / T, t_step = r_step - rr_step * T;
+
+    for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const long long row0 = tile * R;
+        const int rows = (int)((N - row0) < (long long)R ? (N - row0) : (long long)R);
+        for (int ch = 0; ch < chunks; ++ch) {
+            const int cbase = ch * block;
+            const int E = (chunks == 1) ? rows * T : ((T - cbase) < block ? (T - cbase) : block);
+            __syncthreads();                    // previous tile's readers are done
+            int r = r_first, j = j_first, rr = rr_first, t = cbase + t_first;
+            for (int i = tid; i < E * CP; i += block) {             // (k_dense_dsf_coupling's walk)
+                const int dj = t * CP + j;
+                const int cc = col[dj];
+                rec[r * PS + j] = cc >= 0 ? nt_load(pred + (row0 + rr) * stride + cc) : base[dj];
+                r += r_step;
+                rr += rr_step;
+                t += t_step;
+                j += j_step;
+                if (j >= CP) { j -= CP; ++r; ++t; }
+                if (chunks == 1 && t >= T) { t -= T; ++rr; }
+            }
+            __syncthreads();
+            if (tid < E) {
+                long long row = row0;
+                int te = cbase + tid;
+                if (chunks == 1) {
+                    const int re = T_shift >= 0 ? (tid >> T_shift) : (tid / T);
+                    te = tid - re * T;
+                    row = row0 + re;
+                }
+                float *q = rec + tid * PS;
+                (void)dense_extract_record<H>(q, C, L);
+                const long long at = row * D + tgt_idx[te];
+                const float v = x[at];
+                float A = g[at];
+                const float B = gld[row];
+                if (C == 2) {
+                    float unused = 0.0f;
+                    const float mid = dense_comp<H, false, false>(q, L, v, unused);
+                    A = dense_comp_bwd<H>(q + P, L, mid, A, B);
+                }
+                g[at] = dense_comp_bwd<H>(q, L, v, A, B);
+            }
+            __syncthreads();
+            if (dpred) {
+                r = r_first, j = j_first, rr = rr_first, t = cbase + t_first;
+                for (int i = tid; i < E * CP; i += block) {
+                    const int cc = col[t * CP + j];
+                    if (cc >= 0) dpred[(row0 + rr) * stride + cc] = rec[r * PS + j];
+                    r += r_step;
+                    rr += rr_step;
+                    t += t_step;
+                    j += j_step;
+                    if (j >= CP) { j -= CP; ++r; ++t; }
+                    if (chunks == 1 && t >= T) { t -= T; ++rr; }
+                }
+            }
+            // the learned constants: this tile's rows in row order, onto the workgroup's slice
+            const int Tc = chunks == 1 ? T : E, rows_c = chunks == 1 ? rows : 1;
+            int tl = r_first;
+            j = j_first;
+            for (int i = tid; i < Tc * CP; i += block) {
+                const long long dj = (long long)cbase * CP + i;
+                if (col[dj] < 0) {
+                    float sum = 0.0f;
+                    for (int k = 0; k < rows_c; ++k) sum += rec[(k * T + tl) * PS + j];
+                    slice[dj] += sum;
+                }
+                tl += r_step;
+                j += j_step;
+                if (j >= CP) { j -= CP; ++tl; }
+            }
+        }
+    }
+}
+
+// dbase[dj] = the slices' entries dj in slice order (0 where the parameter is predicted)
+__global__ __launch_bounds__(256) void k_dense_bwd_sum(const float *__restrict__ ws, const int *__restrict__ col,
+                                                       float *__restrict__ dbase, long long TCP, int slices)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= TCP) return;
+    float sum = 0.0f;
+    if (col[i] < 0) {
+        for (int k = 0; k < slices; ++k) sum += ws[k * TCP + i];
+    }
+    dbase[i] = sum;
+}
+
+int dense_dsf_coupling_bwd(const float *x, const float *pred, float *g, const float *gld, float *gh, int64_t N, int32_t D,
+                           const int32_t *desc, int32_t T, int32_t n_components, int32_t hidden, int32_t inverse,
+                           void *stream, const char *fn)
+{
+    if (N < 0) return fail(TFK_EINVAL, "%s: N = %lld < 0", fn, (long long)N);
+    if (D < 1 || T < 1 || T > D) return fail(TFK_EINVAL, "%s: need 1 <= T <= D (T = %d, D = %d)", fn, T, D);
+    if (!dense_dsf_supported(n_components, hidden))
+        return fail(TFK_EINVAL, "%s: dense sigmoidal kernels exist for 1 <= hidden size <= 8, 0 <= dense layers <= 2, 1 or 2 "
+                    "components and at most %d parameters per element (n_components = 0x%x, hidden_dim = %d)", fn,
+                    kDenseMaxFloats, (unsigned)n_components, hidden);
+    if (inverse)
+        return fail(TFK_EINVAL, "%s: the inverse direction is a bisection without gradient; differentiate it on the ATen "
+                    "path", fn);
+    if (N == 0) return TFK_OK;                                      // (nothing is written; with null pointers: the probe)
+    if (!x || !g || !gld || !gh || !desc)                           // (pred may be null: every parameter a learned constant)
+        return fail(TFK_EINVAL, "%s: null pointer (the dense family always takes its descriptor block in tgt_idx)", fn);
+    const int C = n_components & 0xff, L = (n_components >> 8) - 1, H = hidden;
+    int T_shift = -1;
+    if ((T & (T - 1)) == 0) {
+        T_shift = 0;
+        while ((1 << T_shift) < T) ++T_shift;
+    }
+    const int P = dense_p(H, L), PS = (C * P) | 1;
+    int block = 256;                                               // (64 records of 513 floats fit)
+    while (block > 64 && (size_t)block * PS * sizeof(float) > kDenseLdsBytes) block >>= 1;
+    const size_t lds = (size_t)block * PS * sizeof(float);
+    const int R = T <= block ? block / T : 1;
+    const int64_t n_tiles = (N + R - 1) / R;
+    int per_cu = (int)(kDenseLdsBytes / lds);
+    if (per_cu > 8) per_cu = 8;
+    int64_t grid = (int64_t)cu_count() * per_cu;
+    if (grid > kDenseBwdSlices) grid = kDenseBwdSlices;
+    if (grid > n_tiles) grid = n_tiles;
+    const size_t TCP = (size_t)T * C * P;
+    float *dbase = gh, *ws = gh + TCP;
+    float *dpred = pred ? gh + (size_t)(1 + kDenseBwdSlices) * TCP : nullptr;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (H) {
+#define TFK_DENSE_CASE(H_)                                                                                          \
+    case H_: {                                                                                                      \
+        auto kern = &k_dense_dsf_coupling_bwd<H_>;                                                                  \
+        if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(kern),                            \
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { \
+            (void)hipGetLastError();                                                                                \
+            return fail(TFK_ELAUNCH, "%s: cannot reserve %zu bytes of LDS", fn, lds);                               \
+        }                                                                                                           \
+        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(block), lds, s, x, pred, g, gld, dpred, ws, (long long)N, D, desc, \
+                           T, T_shift, C, L, P, PS);                                                                \
+    } break;
+        TFK_DENSE_FOR_EACH_H(TFK_DENSE_CASE)
+#undef TFK_DENSE_CASE
+    }
+    if (const int rc = check_launch(fn)) return rc;
+    hipLaunchKernelGGL(k_dense_bwd_sum, dim3((unsigned)((TCP + 255) / 256)), dim3(256), 0, s, ws, desc + T + 1, dbase,
+                       (long long)TCP, (int)grid);
+    return check_launch(fn);
+}
+
 }  // namespace tfk

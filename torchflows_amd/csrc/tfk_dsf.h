@@ -213,5 +213,10 @@ bool dense_dsf_supported(int32_t n_components, int32_t hidden);
 int dense_dsf_coupling(bool inverse, const float *x, const float *pred, float *z, float *logdet, int64_t N, int32_t D,
                        const int32_t *desc, int32_t T, int32_t n_components, int32_t hidden, int32_t accumulate,
                        void *stream, const char *fn);
+// ... and behind tfk_dsf_coupling_bwd: gh = [dL/dbase (T CP) | kDenseBwdSlices x T CP of workspace | dL/dpred (N stride)]
+constexpr int kDenseBwdSlices = 256;        // the most workgroups the reverse-mode launch runs (include/tfk.h states it)
+int dense_dsf_coupling_bwd(const float *x, const float *pred, float *g, const float *gld, float *gh, int64_t N, int32_t D,
+                           const int32_t *desc, int32_t T, int32_t n_components, int32_t hidden, int32_t inverse,
+                           void *stream, const char *fn);
 
 }  // namespace tfk

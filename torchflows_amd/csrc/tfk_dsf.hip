@@ -310,8 +310,7 @@ int tfk_dsf_coupling_bwd(const float *x, const float *h, float *g, const float *
     const char *fn = "tfk_dsf_coupling_bwd";
     const int C = n_components, K = hidden_dim;
     if (dsf_is_dense(n_components))
-        return fail(TFK_EINVAL, "%s: the dense sigmoidal family has no reverse-mode kernel; differentiate it on the ATen "
-                    "path", fn);
+        return dense_dsf_coupling_bwd(x, h, g, gld, gh, N, D, tgt_idx, T, n_components, hidden_dim, inverse, stream, fn);
     if (const int rc = dsf_check(fn, N, D, T, C, K)) return rc;
     if (inverse)
         return fail(TFK_EINVAL, "%s: the inverse direction is a bisection without gradient; differentiate it on the ATen "

@@ -505,6 +505,51 @@ def dsf_coupling_bwd(x, h, g, gld, gh, tgt_idx, T, n_components, hidden_dim, inv
                   (int(n_components), int(hidden_dim)), inverse)
 
 
+DENSE_BWD_SLICES = 256      # include/tfk.h: the workspace of the dense family's reverse mode holds this many slices
+_dense_bwd_probe: Optional[bool] = None
+
+
+def dense_bwd_supported() -> bool:
+    """Does the library have the dense family's reverse-mode kernel?  The probe of include/tfk.h: tfk_dsf_coupling_bwd with
+    the family's code, N = 0 and null pointers -- TFK_EINVAL from a library without it; no device is touched."""
+    global _dense_bwd_probe
+    if _dense_bwd_probe is None:
+        _dense_bwd_probe = lib().tfk_dsf_coupling_bwd(None, None, None, None, None, 0, 1, None, 1, dense_code(1, 0), 1, 0,
+                                                      None) == 0
+    return _dense_bwd_probe
+
+
+def dense_bwd_floats(N, T, per_target, stride):
+    """(dL/dbase, workspace, dL/dpred) floats of the ``gh`` block tfk_dsf_coupling_bwd takes for the dense family."""
+    tcp = int(T) * int(per_target)
+    return tcp, DENSE_BWD_SLICES * tcp, int(N) * int(stride)
+
+
+def dense_coupling_bwd(x, pred, g, gld, gh, desc, T, n_components, n_dense_layers, hidden_size, inverse=False):
+    """Reverse mode of ``dense_coupling`` (forward direction only): in place on g (N, D) at the target columns.  ``gh``: the
+    block of ``dense_bwd_floats`` or None to have it allocated here (dL/dpred zero-filled: the kernel stores only the columns
+    the descriptor names).  Returns (dL/dpred (N, stride) or None when ``pred`` is, dL/dbase (T C P)), views of it."""
+    name = "tfk_dsf_coupling_bwd"
+    N, D = _bwd_common(name, x, g, gld, None, T)
+    CP = (desc.numel() - T - 1) // (2 * T)
+    if desc.numel() != T + 1 + 2 * T * CP or int(T) > D:
+        raise NativeError(f"{name}: a descriptor of {desc.numel()} entries does not fit T = {T} targets of D = {D} columns")
+    if pred is not None and (pred.dim() != 2 or pred.shape[0] != N):
+        raise NativeError(f"{name}: the predicted block has shape {tuple(pred.shape)}, expected ({N}, stride)")
+    n_base, n_ws, n_pred = dense_bwd_floats(N, T, CP, 0 if pred is None else pred.shape[1])
+    if gh is None:
+        gh = torch.empty(n_base + n_ws + n_pred, dtype=torch.float32, device=g.device)
+        gh[n_base + n_ws:].zero_()
+        if N == 0:
+            gh[:n_base].zero_()
+    elif gh.numel() != n_base + n_ws + n_pred:
+        raise NativeError(f"{name}: gh has {gh.numel()} elements, expected T*C*P * (1 + {DENSE_BWD_SLICES}) + N*stride = "
+                          f"{n_base + n_ws + n_pred}")
+    _launch(name, g, _f32(x, name), _f32(pred, name), _f32(g, name), _f32(gld, name), _f32(gh, name), N, D, _idx(desc, name), T,
+            dense_code(n_components, n_dense_layers), int(hidden_size), 1 if inverse else 0)
+    return (None if pred is None else gh[n_base + n_ws:].view(N, -1)), gh[:n_base]
+
+
 # ---- the transformer kinds (``transformer.native_kind``): which wrappers serve each, with which scalar arguments, and when
 # there is a kernel -- what the layers (layers_base.py) and the training chain (autograd.py) ask instead of naming kinds.
 def _dsf_native(tr) -> bool:
@@ -524,6 +569,13 @@ def _dense_native(tr) -> bool:
     if debug_switch("dense", "1") == "0":
         return False
     return dsf_supported(dense_code(tr.n_components, tr.n_dense_layers), tr.hidden_size)
+
+
+def _dense_train_native(tr) -> bool:
+    """... with the reverse-mode kernel on top (``dense_bwd_supported``); TORCHFLOWS_AMD_DEBUG="dense_train=0" turns only that
+    off: evaluation stays on the kernel, training takes the ATen graph (A/B runs, tools/dense_rows.py)."""
+    from torchflows_amd.utils import debug_switch
+    return debug_switch("dense_train", "1") != "0" and _dense_native(tr) and dense_bwd_supported()
 
 
 def _always(tr) -> bool:
@@ -563,8 +615,9 @@ KINDS = {
     "dsf": TransformerKind("dsf_coupling", "dsf_coupling_bwd", attrgetter("n_components", "hidden_dim"), False,
                            _dsf_native, _dsf_native, _dsf_native),
     # (h: the conditioner's predicted block, tgt: the layer's descriptor block -- layers_base.py: _dense_inputs)
-    "dense": TransformerKind("dense_coupling", "", attrgetter("n_components", "n_dense_layers", "hidden_size"), False,
-                             _dense_native, _dense_native, _never),
+    # (... and gh None: the reverse wrapper allocates its block and returns (dL/dpred, dL/dbase))
+    "dense": TransformerKind("dense_coupling", "dense_coupling_bwd", attrgetter("n_components", "n_dense_layers", "hidden_size"),
+                             False, _dense_native, _dense_native, _dense_train_native),
     "conv1x1": TransformerKind("conv1x1_coupling", "conv1x1_coupling_bwd", lambda tr: (tr.n_channels,), False,
                                lambda tr: tr.n_channels <= 16,      # channels are kept in registers
                                _never, lambda tr: int(tr.n_channels) <= 16),
@@ -603,13 +656,14 @@ def transform(tr, inverse, x, h, out, logdet, tgt, T, accumulate):
 
 
 def transform_bwd(tr, inverse, x, h, g, gld, gh, tgt, T):
-    """Reverse mode of ``transform``: in place on ``g`` at the target columns, dL/dh written to ``gh``."""
+    """Reverse mode of ``transform``: in place on ``g`` at the target columns, dL/dh written to ``gh``.  Returns what the
+    wrapper does (the dense family's (dL/dpred, dL/dbase))."""
     kind = KINDS.get(tr.native_kind)
     if kind is None:
         raise NativeError(f"no kernel for transformer kind {tr.native_kind!r}")
     extra = kind.scalars(tr) if kind.scalars is not None else ()
     lead = (x, h, g, gld, gh) if kind.reverse_reads_x else (g, gh)
-    globals()[kind.reverse](*lead, tgt, T, *extra, inverse=inverse != kind.flipped)
+    return globals()[kind.reverse](*lead, tgt, T, *extra, inverse=inverse != kind.flipped)
 
 
 def elementwise_affine_bwd(x, value, g, gld, want_param, inverse=False, out=None):
