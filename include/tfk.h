@@ -467,7 +467,16 @@ int tfk_made_affine_sequential(const float *z, float *x, float *logdet, int64_t 
  * come from rows [23 i, 23 i + 23) of W2 (D, 23, hidden_padded), b2 (D, 23); the spline is inverted
  * (rational_quadratic.py:147-200).  hidden_padded in {8, 16}.  The log-det is the one the reference returns:
  * that of its LAST pass (layers_base.py:213-221), i.e. elements j < D-1 evaluated at their inverted values.
- * tfk_made_rqs_sequential_lds_bytes: LDS the launch needs at its smallest workgroup (must be <= 160 KiB). */
+ * n_bins = 1 << 16 | C << 8 | K instead: the same walk for a MADE-based DEEP SIGMOIDAL layer (Sigmoid / DeepSigmoid,
+ * C components of K hidden units; csrc/tfk_made_dsf.hip): W2 (D, 3 K C, hidden_padded), b2 (D, 3 K C) in the
+ * conditioner's own record order (per component [da (K) | db (K) | dw (K)]), every (C, K) of tfk_dsf_supported,
+ * hidden_padded in {8, 16}; each element is inverted by the bisection of tfk_dsf_coupling_inv, and once more at its
+ * inverted value for the log-det of the last pass.  boundary is the half-width of the bisection bracket and must be
+ * 10.0.  Any other n_bins but 8 is TFK_EINVAL.
+ * tfk_made_rqs_sequential_lds_bytes: LDS the launch needs at its smallest workgroup (must be <= 160 KiB).  With a deep
+ * sigmoidal code: 4 (align4(D hp + hp + D P + (64 / G) (D + 1)) + 2 P hp) bytes, P = 3 K C, G = 4 / 8 / 16 the smallest
+ * not below K (W2 streamed through two slices); a value above 160 KiB for a (C, K) or hidden_padded without a kernel.
+ * Needs no device. */
 int64_t tfk_made_rqs_sequential_lds_bytes(int32_t D, int32_t hidden_padded, int32_t n_bins);
 int tfk_made_rqs_sequential(const float *z, float *x, float *logdet, int64_t N, int32_t D,
                             const float *W1t, const float *b1, const float *W2, const float *b2,

@@ -3,6 +3,7 @@
 call, the median of 100 after warm-up.
 
     python tools/dsf_rows.py [--rows 65536] [--reps 100] [--aten-reps 5] [--tag NAME]
+    python tools/dsf_rows.py --legs made --rows 16384       (the MADE twins' sequential map, both routes: made_legs below)
 
 One JSON line per measurement:
   * ``tfk_dsf_coupling_fwd`` / ``tfk_dsf_coupling_inv`` alone, on the rows and the parameters h the flow's first coupling
@@ -73,8 +74,64 @@ def report(**kw):
     print(json.dumps(kw), flush=True)
 
 
+def made_legs(args):
+    """``--legs made``: the sequential map of the MADE twins -- ``sample`` of MaskedAutoregressiveDeepSF(64, n_layers=8) and
+    ``log_prob`` of InverseAutoregressiveDeepSF(64, n_layers=8) -- on the one-launch route (csrc/tfk_made_dsf.hip) and on
+    the host loop of D passes of the same build (TORCHFLOWS_AMD_DEBUG="made_fused=0"), the two routes taking turns call
+    by call; and the mean bisection trips of the first layer's sequential map (both bisections of an element run on the
+    same record, so the re-enactment at z stands for either)."""
+    import torchflows_amd as tfa
+    from torchflows_amd import native
+    N, D = args.rows, 64
+    x = torch.randn(N, D, device="cuda")
+    for arch, what in (("MaskedAutoregressiveDeepSF", "sample"), ("InverseAutoregressiveDeepSF", "log_prob")):
+        torch.manual_seed(0)
+        flow = tfa.Flow(getattr(tfa, arch)(D, n_layers=8))
+        flow.train()
+        with torch.no_grad():
+            flow.log_prob(torch.randn(256, D))
+        flow = flow.eval().cuda()
+        fn = (lambda: flow.sample((N,), return_log_prob=True)) if what == "sample" else (lambda: flow.log_prob(x))
+        routes = (("one launch per layer", None), ("host loop of D passes (made_fused=0)", "made_fused=0"))
+        us, launches = {r: [] for r, _ in routes}, {}
+        prev = os.environ.get("TORCHFLOWS_AMD_DEBUG")
+        with torch.no_grad():
+            for rep in range(-1, max(args.aten_reps, 5)):         # (-1: warm-up of both routes)
+                for route, switch in routes:
+                    if switch:
+                        os.environ["TORCHFLOWS_AMD_DEBUG"] = ",".join(v for v in (prev, switch) if v)
+                    try:
+                        before = native.calls
+                        t = timed(fn, 1, warmup=0)
+                        launches[route] = native.calls - before
+                    finally:
+                        if prev is None:
+                            os.environ.pop("TORCHFLOWS_AMD_DEBUG", None)
+                        else:
+                            os.environ["TORCHFLOWS_AMD_DEBUG"] = prev
+                    if rep >= 0:
+                        us[route] += t
+            layer = next(l for l in flow.bijection.layers if hasattr(l, "_made_pack"))
+            n = min(N, 4096)
+            z = x[:n]
+            xs, _ = layer.inverse(z) if what == "sample" else layer.forward(z)
+            tr = layer.transformer
+            h = layer.conditioner_transform(xs).reshape(n, D, -1)
+            trips = trip_counts(tr, z, h)
+        for route, _ in routes:
+            t = us[route]
+            report(tag=args.tag, model=f"{arch}(64, n_layers=8)", call=what, route=route, rows=N, D=D, calls_timed=len(t),
+                   libtfk_launches=launches[route], us_per_call=round(statistics.median(t), 1), us_min=round(min(t), 1),
+                   us_max=round(max(t), 1), evals_per_s=round(N / statistics.median(t) * 1e6))
+        report(tag=args.tag, model=f"{arch}(64, n_layers=8)", call="bisection trips, first layer", rows=n,
+               n_components=tr.n_components, hidden_dim=tr.hidden_dim,
+               mean_trips_per_component=round(float(trips.mean()) / tr.n_components, 2), max_trips_per_element=int(trips.max()))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--legs", choices=("coupling", "made"), default="coupling",
+                    help="made: the MADE twins' sequential map on both routes (use --rows 16384)")
     ap.add_argument("--rows", type=int, default=1 << 16)
     ap.add_argument("--reps", type=int, default=100)
     ap.add_argument("--aten-reps", type=int, default=5)
@@ -86,6 +143,8 @@ def main():
     import torchflows_amd as tfa
     from torchflows_amd import native
     warnings.simplefilter("ignore")
+    if args.legs == "made":
+        return made_legs(args)
     N, D = args.rows, 64
     name = "CouplingDeepSF(64, n_layers=8)"
     torch.manual_seed(0)

@@ -274,10 +274,12 @@ class MaskedAutoregressiveBijection(AutoregressiveBijection):
 
     def _made_pack(self):
         """(W1t, b1, W2, b2) for tfk_made_affine_sequential / tfk_made_rqs_sequential -- masked,
-        transposed, zero-padded to 8 / 16 / 32 / 64 hidden units -- when the layer qualifies (affine or
-        8-bin RQ-spline transformer, MADE with two masked linear layers and no global parameters); cached
-        until a weight changes.  None for a deep sigmoidal transformer: its sequential map is the host loop of D
-        passes below, one tfk_dsf_coupling_inv launch (bisection included) each."""
+        transposed, zero-padded to 8 / 16 / 32 / 64 hidden units -- when the layer qualifies (affine, 8-bin
+        RQ / linear rational spline or deep sigmoidal transformer, MADE with two masked linear layers and no global
+        parameters, LDS probe of the library); cached until a weight changes.  A deep sigmoidal layer
+        (csrc/tfk_made_dsf.hip, P = 3 K C) also declines under TORCHFLOWS_AMD_FUSED=0: that variable means the per-layer
+        entry points around PyTorch-ROCm conditioner GEMMs, and this launch folds the conditioner in.  None sends the
+        sequential map to the host loop of D passes below (for a dense sigmoidal layer: always)."""
         import torch.nn as nn
         from torchflows_amd import fused
         from torchflows_amd.utils import debug_switch
@@ -287,9 +289,13 @@ class MaskedAutoregressiveBijection(AutoregressiveBijection):
         kind = self.transformer.native_kind
         if kind in ("rqs", "lrs") and self.transformer.n_bins != 8:
             return None
-        if kind not in ("affine", "inverse_affine", "rqs", "lrs") or ct.n_global_parameters != 0:
+        if kind not in ("affine", "inverse_affine", "rqs", "lrs", "dsf") or ct.n_global_parameters != 0:
+            return None
+        if kind == "dsf" and not fused.enabled():
             return None
         P = {"rqs": 23, "lrs": 32}.get(kind, 2)
+        if kind == "dsf":
+            P = 3 * self.transformer.hidden_dim * self.transformer.n_components
         mods = list(ct.sequential)
         if not (len(mods) == 3 and isinstance(mods[0], MADE.MaskedLinear) and isinstance(mods[1], nn.Tanh)
                 and isinstance(mods[2], MADE.MaskedLinear)):
@@ -303,16 +309,18 @@ class MaskedAutoregressiveBijection(AutoregressiveBijection):
         if hit is not None and hit[0] == version:
             return hit[1]
         HP = 8 if H <= 8 else (16 if H <= 16 else (32 if H <= 32 else 64))
-        if kind in ("rqs", "lrs"):
-            need = (native.lib().tfk_made_rqs_sequential_lds_bytes if kind == "rqs"
-                    else native.lib().tfk_made_lrs_sequential_lds_bytes)
-            if HP > 16 or need(D, HP, 8) > 160 * 1024:
+        if kind in ("rqs", "lrs", "dsf"):
+            need = (native.lib().tfk_made_lrs_sequential_lds_bytes if kind == "lrs"
+                    else native.lib().tfk_made_rqs_sequential_lds_bytes)
+            code = (native.made_dsf_code(self.transformer.n_components, self.transformer.hidden_dim) if kind == "dsf"
+                    else 8)
+            if HP > 16 or need(D, HP, code) > 160 * 1024:
                 return None
         elif 4 * (3 * D * HP + HP + 2 * D) + 4 * 64 * (D + 1) > 160 * 1024:
             return None                                  # weights + 64 staged rows do not fit the LDS
         with torch.no_grad():
             w1 = mods[0].weight * mods[0].mask                       # (H, D)
-            w2 = mods[2].weight * mods[2].mask                       # (2 D, H)
+            w2 = mods[2].weight * mods[2].mask                       # (P D, H)
             W1t = w1.new_zeros(D, HP)
             W1t[:, :H] = w1.t()
             b1 = w1.new_zeros(HP)
@@ -336,7 +344,10 @@ class MaskedAutoregressiveBijection(AutoregressiveBijection):
         packed = self._made_pack() if context is None else None
         if packed is not None:                               # the D passes in ONE launch (tfk_made.hip)
             out = rows if state.owned else state.out_buffer()
-            if self.transformer.native_kind in ("rqs", "lrs"):
+            if self.transformer.native_kind == "dsf":
+                native.made_dsf_sequential(rows, out, state.logdet, *packed, self.transformer.n_components,
+                                           self.transformer.hidden_dim, accumulate=state.started)
+            elif self.transformer.native_kind in ("rqs", "lrs"):
                 native.made_rqs_sequential(rows, out, state.logdet, *packed, self.transformer.n_bins,
                                            self.transformer.boundary, accumulate=state.started,
                                            lrs=self.transformer.native_kind == "lrs")

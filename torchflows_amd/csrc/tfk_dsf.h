@@ -219,4 +219,15 @@ int dense_dsf_coupling_bwd(const float *x, const float *pred, float *g, const fl
                            const int32_t *desc, int32_t T, int32_t n_components, int32_t hidden, int32_t inverse,
                            void *stream, const char *fn);
 
+// the (C, K) the coupling kernels of tfk_dsf.hip and the sequential MADE kernel of tfk_made_dsf.hip are instantiated for
+inline bool dsf_supported(int C, int K) { return K >= 1 && C >= 1 && ((K <= 16 && C <= 2) || (K <= 8 && C <= 4)); }
+
+// ---- the sequential map of a MADE-based deep sigmoidal layer (tfk_made_dsf.hip) behind tfk_made_rqs_sequential /
+// tfk_made_rqs_sequential_lds_bytes: n_bins carries 1 << 16 | C << 8 | K (include/tfk.h) ----
+inline bool made_is_dsf(int32_t n_bins) { return (n_bins >> 16) == 1; }
+int64_t made_dsf_sequential_lds_bytes(int32_t D, int32_t hidden_padded, int32_t code);
+int made_dsf_sequential(const float *z, float *x, float *logdet, int64_t N, int32_t D, const float *W1t, const float *b1,
+                        const float *W2, const float *b2, int32_t hidden_padded, int32_t code, float boundary,
+                        int32_t accumulate, void *stream, const char *fn);
+
 }  // namespace tfk

@@ -215,11 +215,6 @@ __global__ __launch_bounds__(dsf_block(K)) void k_dsf_coupling_bwd(
     }
 }
 
-static bool dsf_supported(int C, int K)
-{
-    return K >= 1 && C >= 1 && ((K <= 16 && C <= 2) || (K <= 8 && C <= 4));
-}
-
 static int dsf_check(const char *fn, int64_t N, int32_t D, int32_t T, int32_t C, int32_t K)
 {
     if (N < 0) return fail(TFK_EINVAL, "%s: N = %lld < 0", fn, (long long)N);

@@ -19,6 +19,7 @@
 #include "tfk_common.h"
 #include "tfk_spline.h"
 #include "tfk_lrs.h"
+#include "tfk_dsf.h"                // made_is_dsf / made_dsf_sequential: the deep sigmoidal walk of tfk_made_dsf.hip
 
 namespace tfk {
 
@@ -294,6 +295,7 @@ int tfk_made_lrs_sequential(const float *z, float *x, float *logdet, int64_t N, 
 
 int64_t tfk_made_rqs_sequential_lds_bytes(int32_t D, int32_t hidden_padded, int32_t n_bins)
 {
+    if (made_is_dsf(n_bins)) return made_dsf_sequential_lds_bytes(D, hidden_padded, n_bins);
     const int64_t P = 3 * (int64_t)n_bins - 1;
     // weights + 64 staged rows (the smallest workgroup)
     return 4 * ((int64_t)D * hidden_padded + hidden_padded + P * D * hidden_padded + P * D) + 4 * 64 * ((int64_t)D + 1);
@@ -305,6 +307,8 @@ int tfk_made_rqs_sequential(const float *z, float *x, float *logdet, int64_t N, 
                             void *stream)
 {
     const char *fn = "tfk_made_rqs_sequential";
+    if (made_is_dsf(n_bins))
+        return made_dsf_sequential(z, x, logdet, N, D, W1t, b1, W2, b2, hidden_padded, n_bins, boundary, accumulate, stream, fn);
     if (N < 0) return fail(TFK_EINVAL, "%s: N = %lld < 0", fn, (long long)N);
     if (D < 1 || D > 1024) return fail(TFK_EINVAL, "%s: D = %d not in [1, 1024]", fn, D);
     if (hidden_padded != 8 && hidden_padded != 16) return fail(TFK_EINVAL, "%s: hidden_padded = %d must be 8 or 16", fn, hidden_padded);

@@ -823,6 +823,27 @@ def made_rqs_sequential(z, out, logdet, W1t, b1, W2, b2, n_bins, boundary, accum
             _f32(W2, name), _f32(b2, name), HP, int(n_bins), C.c_float(float(boundary)), 1 if accumulate else 0)
 
 
+def made_dsf_code(n_components, hidden_dim) -> int:
+    """What a MADE-based deep sigmoidal layer passes as ``n_bins`` of tfk_made_rqs_sequential and its probe:
+    1 << 16 | C << 8 | K (include/tfk.h)."""
+    return (1 << 16) | (int(n_components) << 8) | int(hidden_dim)
+
+
+def made_dsf_sequential(z, out, logdet, W1t, b1, W2, b2, n_components, hidden_dim, accumulate=False):
+    """The sequential map of a MADE-based deep sigmoidal layer in one launch (csrc/tfk_made_dsf.hip, reached through
+    tfk_made_rqs_sequential); W1t (D, HP), b1 (HP,), W2 (D, P, HP), b2 (D, P) masked and zero-padded to HP hidden units,
+    P = 3 hidden_dim n_components in the conditioner's own record order.  ``out`` may be ``z``."""
+    name = "tfk_made_rqs_sequential"
+    N, D = _rows(z, name)
+    HP, P = b1.numel(), 3 * int(hidden_dim) * int(n_components)
+    if out.shape != z.shape or logdet.numel() != N or W1t.numel() != D * HP or W2.numel() != P * D * HP \
+            or b2.numel() != P * D:
+        raise NativeError(f"{name}: bad tensor shapes for a deep sigmoidal layer of {n_components} x {hidden_dim}")
+    _launch(name, z, _f32(z, name), _f32(out, name), _f32(logdet, name), N, D, _f32(W1t, name), _f32(b1, name),
+            _f32(W2, name), _f32(b2, name), HP, made_dsf_code(n_components, hidden_dim), C.c_float(10.0),
+            1 if accumulate else 0)
+
+
 def conv3x3_relu_pool_affine(x, weight, bias, scale, shift):
     """conv3x3(pad 1) -> ReLU -> MaxPool2d(2) -> per-channel scale / shift in one launch (NCHW)."""
     name = "tfk_conv3x3_relu_pool_affine"
