@@ -804,7 +804,13 @@ int tfk_affine_coupling_train_bwd(const float *x, float *g, const float *gld, co
  *   gh_perm   (N, 768): column (6 e + c) * 16 + 4 q + r = dL/d(parameter 4c + r of target element 8q + e)
  *   gpre_perm (N, 16):  column 4 q + r = dL/d(pre-activation of hidden unit 4 r + q)
  * params: A1[8][64] | b1[16] | A2[48][gemm2_steps][64] | b2[48][16] | A2T[48][4][64] | A1T[2][4][64]
- * (csrc/tfk_bwd.hip; packed by torchflows_amd/autograd.py:_RqsTrainPack). */
+ * (csrc/tfk_bwd.hip; packed by torchflows_amd/autograd.py:_RqsTrainPack).
+ * n_bins = (1 << 16) | 8: the same for a LINEAR RATIONAL spline coupling (csrc/tfk_lrs.hip), 32 parameters = 8 tiles per
+ * element; tfk_rqs_coupling_train_bwd_supported(64, (1 << 16) | 8) == 1, every other value with a bit above the low 16: 0.
+ *   gh_perm   (N, 1024): column (8 e + c) * 16 + 4 q + r = dL/d(parameter 4c + r of target element 8q + e)
+ *   params: A1[8][64] | b1[16] | A2[64][gemm2_steps][64] | b2[64][16] | A2T[64][4][64] | A1T[2][4][64], tile 8 e + c:
+ *   18 448 + 4 096 * gemm2_steps floats (34 832 = 139 328 bytes at 4 steps, resident in the LDS;
+ *   torchflows_amd/train_packs.py:_LrsTrainPack).  gpre_perm, hid_perm and the other arguments are unchanged. */
 int tfk_rqs_coupling_train_bwd_supported(int32_t D, int32_t n_bins);
 int tfk_rqs_coupling_train_bwd(const float *x, float *g, const float *gld, const float *params,
                                int64_t n_params, int32_t gemm2_steps, float *gh_perm, float *gpre_perm,

@@ -42,8 +42,8 @@ import torch
 from torchflows_amd.utils import debug_switch
 
 from torchflows_amd import native
-from torchflows_amd.flow_compile import _flatten
-from torchflows_amd.train_packs import (_LAYOUTS, _RqsTrainPack, _TrainPack, _WideTrainPack,  # noqa: F401
+from torchflows_amd.flow_compile import _flatten, _lean_spline_extra
+from torchflows_amd.train_packs import (_LAYOUTS, _LrsTrainPack, _RqsTrainPack, _TrainPack, _WideTrainPack,  # noqa: F401
                                         reversal_index, training_layout)
 
 FORWARD, INVERSE = 0, 1
@@ -290,6 +290,19 @@ def _fused_rqs_layer(layer, D: int):
     return mlp if (mlp is not None and mlp[0].out_features <= 16) else None
 
 
+def _fused_lrs_layer(layer, D: int):
+    """(lin1, lin2) when the layer trains on the linear-rational-spline launches: a one-op lean program forward, the LRS form
+    of tfk_rqs_coupling_train_bwd backward -- 8 bins, D = 64 exactly (no padding: other event sizes keep the layer-by-layer
+    route), HalfSplit, the plain conditioner in float32 with a hidden width <= 16."""
+    if not fused_train_enabled() or D != 64 or layer.transformer.native_kind != "lrs":
+        return None
+    K = int(layer.transformer.n_bins)
+    if K != 8 or not native.lib().tfk_rqs_coupling_train_bwd_supported(D, native.LRS_TRAIN_FLAG | K):
+        return None
+    mlp = _half_split_mlp(layer, D, ("lrs",), fp32=True)
+    return mlp if (mlp is not None and mlp[0].out_features <= 16) else None
+
+
 def flat_enabled() -> bool:
     """Operands gathered from / gradients returned as slices of ONE buffer when the parameters live in one
     (torchflows_amd/flat_optim.py; TORCHFLOWS_AMD_DEBUG=flat=0: always the per-tensor route)."""
@@ -407,13 +420,13 @@ def _fold_after(plan, i: int, fold: bool, fold_rev: bool):
 # The route of a step, resolved once per plan (_PlanPacks.routes): its kind in the plan unless it is a coupling (on fused
 # launches or layer by layer) or rides along with one; its forward and backward functions: _STEPS[route].
 _FOLDED, _PERM, _ELEMENTWISE, _ELEMENTWISE_CTX, _MADE = "folded", "perm", "elementwise", "elementwise_ctx", "made"
-_AFFINE, _RQS, _WIDE, _LAYERWISE = "affine", "rqs", "wide", "layerwise"
+_AFFINE, _RQS, _WIDE, _LRS, _LAYERWISE = "affine", "rqs", "wide", "lrs", "layerwise"
 
 
 class _FusedCoupling(NamedTuple):
     """One coupling on fused training launches."""
     step: int                       # index in the plan
-    route: str                      # _AFFINE (_TrainPack), _RQS (_RqsTrainPack) or _WIDE (_WideTrainPack)
+    route: str                      # _AFFINE (_TrainPack), _RQS (_RqsTrainPack), _WIDE (_WideTrainPack) or _LRS (_LrsTrainPack)
     k: int                          # index among the plan's couplings of the same route: its packed block
     lin1: torch.nn.Module
     lin2: torch.nn.Module
@@ -452,7 +465,7 @@ class _PlanPacks:
         self.records: List[_FusedCoupling] = []
         self.record_at: List[Optional[_FusedCoupling]] = [None] * len(plan)
         self.routes = [_LAYERWISE if kind == "coupling" else kind for _, _, kind in plan]
-        self.fused = by_route = {_AFFINE: [], _RQS: [], _WIDE: []}
+        self.fused = by_route = {_AFFINE: [], _RQS: [], _WIDE: [], _LRS: []}
         pidx, gidx, off_flat, off_out = [], [], 0, 0                  # AFFINE: operand gather, accumulator gather
         widx, wmul, wadd, off_wide = [], [], [], 0                    # WIDE: operand gather and its float64 pre-scaling
         for i, (layer, d, kind) in enumerate(plan):
@@ -466,6 +479,8 @@ class _PlanPacks:
                 pack = _TrainPack.get(W, mlp[0].out_features, device, D, shift=shift)
             elif route == _RQS:
                 pack = _RqsTrainPack.get(mlp[0].out_features, device, D)
+            elif route == _LRS:
+                pack = _LrsTrainPack.get(mlp[0].out_features, device)
             else:
                 pack = _WideTrainPack.get(D, mlp[0].out_features, device, shift)
                 lean = (2 + (d == INVERSE)) if shift else int(_affine_form_is_inverse(layer, d))
@@ -502,7 +517,7 @@ class _PlanPacks:
 
     def _fused_route(self, layer, fusable: bool):
         """(route, (lin1, lin2)) of a coupling that runs on fused launches at this plan's row width, else (None, None): the
-        affine launches first, then the wide ones, then the spline's."""
+        affine launches first, then the wide ones, then the RQ spline's, then the linear rational spline's."""
         mlp = _fused_bwd_layer(layer, self.D) if fusable else None
         if mlp is not None:
             return _AFFINE, mlp
@@ -511,7 +526,10 @@ class _PlanPacks:
             return _WIDE, mlp
         K = int(getattr(layer.transformer, "n_bins", 0) or 0)
         mlp = _fused_rqs_layer(layer, self.D) if native.lib().tfk_rqs_coupling_train_bwd_supported(self.W, K) else None
-        return (_RQS, mlp) if mlp is not None else (None, None)
+        if mlp is not None:
+            return _RQS, mlp
+        mlp = _fused_lrs_layer(layer, self.D) if self.W == self.D else None
+        return (_LRS, mlp) if mlp is not None else (None, None)
 
     # ---- parameters that live in ONE buffer (torchflows_amd/flat_optim.py) --------------------------------------
     def flat_capable(self) -> bool:
@@ -519,7 +537,7 @@ class _PlanPacks:
         all gradients of the plan then come out of libtfk accumulators and can leave as slices of one buffer."""
         if not self.fused[_AFFINE] and not self.fused[_RQS]:
             return False
-        if self.fused[_WIDE]:                 # (wide couplings return their gradients per tensor: no one-buffer maps yet)
+        if self.fused[_WIDE] or self.fused[_LRS]:     # (these return their gradients per tensor: no one-buffer maps yet)
             return False
         # ONE layer object (or one parameter tensor) twice in the chain (shared weights): grad_src maps a slot of the parameter buffer to exactly
         # one accumulator position, so the second use would overwrite the first instead of adding to it -- such a plan
@@ -709,6 +727,30 @@ class _PlanPacks:
         return list(packed.split(self.wide_sizes))
 
 
+    def pack_lrs(self):
+        """[(forward program block, backward operand block)] per linear-rational-spline coupling for the current weights.  The
+        couplings of one hidden width are packed together: one stack, one gather each way, one float64 multiply-add and one
+        bf16 split for all of them -- device tensor ops only.  The closing TFK_OP_EW_FMA block of the fixed elementwise layer
+        that rides along lies behind the forward block (the identity, unused, when none does)."""
+        out = [None] * len(self.fused[_LRS])
+        groups = {}
+        for rec in self.fused[_LRS]:
+            groups.setdefault(id(rec.pack), []).append(rec)
+        for group in groups.values():
+            pack = group[0].pack
+            flats = torch.stack([torch.cat(pack.flat_of(rec.lin1, rec.lin2)) for rec in group])
+            bwd = flats.index_select(1, pack.param_index)
+            ew = [pack.ew_identity if rec.ew_step is None else
+                  _ew_fma_block(self.plan[rec.ew_step][0], self.plan[rec.ew_step][1], self.D, pack.hp)[0] for rec in group]
+            if pack.H <= 15:
+                fwd = torch.cat([pack.forward_blocks(flats), torch.stack(ew)], dim=1)
+            else:                             # two hidden tiles: the inference packer itself, layer by layer
+                fwd = [torch.cat([pack.forward_block_wide(rec.lin1, rec.lin2), e]) for rec, e in zip(group, ew)]
+            for n, rec in enumerate(group):
+                out[rec.k] = (fwd[n], bwd[n])
+        return out
+
+
 def _plan_packs(plan, D: int, device, fold: bool) -> _PlanPacks:
     owner = plan[0][0]
     key = (tuple(id(l) for l, _, _ in plan), tuple(d for _, d, _ in plan), str(device),
@@ -738,7 +780,13 @@ def fully_fused(plan, D: int) -> bool:
     def spline_ok(layer):
         mlp = _fused_rqs_layer(layer, D)
         return mlp is not None and rows_outer_enabled() and mlp[0].out_features <= 15
-    return plan_width(plan, D) == 64 and all(spline_ok(layer) for layer in couplings)
+    if plan_width(plan, D) == 64 and all(spline_ok(layer) for layer in couplings):
+        return True
+    # linear-rational-spline couplings at 64 columns: the lean program, the fused launch and tfk_rows_outer likewise
+    def lrs_ok(layer):
+        mlp = _fused_lrs_layer(layer, D)
+        return mlp is not None and rows_outer_enabled() and mlp[0].out_features <= 15
+    return D == 64 and all(lrs_ok(layer) for layer in couplings)
 
 
 SPLIT_K_ROWS = 1024
@@ -853,7 +901,7 @@ def _folded_gscale(packs: _PlanPacks, rec: _FusedCoupling, packed: Optional[torc
     if rec.ew_step is None:
         return None
     ew_layer, ew_d, _ = packs.plan[rec.ew_step]
-    if rec.route == _WIDE:
+    if rec.route in (_WIDE, _LRS):
         return _ew_fma_block(ew_layer, ew_d, packs.D, rec.pack.hp)[1]           # d(s x + t)/dx = s
     W = packs.W
     block, lo = (_ew_block(ew_layer, ew_d, packs.D, W), 0) if packed is None else (packed, rec.pack.param_index.numel())
@@ -1135,6 +1183,45 @@ def _bwd_rqs(st, i, layer, d):               # conditioner re-evaluated in the k
     st.grads_per_step[i] = _mlp_param_grads(cparams, lin1, lin2, dW1b[:, :-1], dW1b[:, -1], dW2b[:, :-1], dW2b[:, -1])
 
 
+def _fwd_lrs(st, step, layer, d):
+    # conditioner + linear rational spline (+ the fixed elementwise layer and the reversal that follow) as a one-op lean
+    # program (bf16 x 3 operands, the inference kernel) on the block packed from the live weights
+    rec = st.packs.record_at[step]
+    rp = rec.pack
+    prm = st.packed[_LRS][rec.k][0]
+    n_fwd = prm.numel() - rp.N_EW
+    ops = [(rp.ops[d == INVERSE], 0, rp.fwd_steps2, 0) + _lean_spline_extra(layer.transformer, True, rp.fmt)]
+    if rec.ew_step is not None:
+        ops.append((rp.op_ew_fma, 0, 0, n_fwd))
+    st.program(native.flow_run_mfma, rec, ops, prm if rec.ew_step is not None else prm[:n_fwd])
+
+
+def _bwd_lrs(st, i, layer, d):               # conditioner re-evaluated in the kernel, dL/dh written once
+    rec = st.packs.record_at[i]
+    rp, lin1, lin2 = rec.pack, rec.lin1, rec.lin2
+    x_in, g, N = st.saved[i], st.g, st.N
+    cparams = _module_params(layer.conditioner_transform)
+    gh_perm, gpre_perm, hid_perm = rp.records(N)
+    outer = rows_outer_enabled() and rp.H <= 15
+    native.lrs_coupling_train_bwd(x_in, g, st.gld, st.packed[_LRS][rec.k][1], rp.steps2, gh_perm, gpre_perm,
+                                  layer.transformer.n_bins, layer.transformer.boundary, inverse=(d == INVERSE),
+                                  gscale=_folded_gscale(st.packs, rec), g_reversed=rec.rev_step is not None,
+                                  hid_perm=hid_perm if outer else None)
+    if outer:                                # the three row-contracting products, un-permuted by ONE gather
+        acc = torch.empty(rp.n_acc, dtype=torch.float32, device=g.device)
+        _weight_products(x_in, 32, gh_perm, 1024, gpre_perm, hid_perm, acc)
+        grads = (t.view(shp) for t, shp in zip(acc.index_select(0, rp.acc_index).split(rp.acc_sizes), rp.acc_shapes))
+        st.grads_per_step[i] = _mlp_param_grads(cparams, lin1, lin2, *grads)
+        return
+    x_a = x_in[:, :32]                       # hidden width 16 / rows_outer off: split-K GEMMs on the GEMM library
+    a1 = torch.tanh(torch.addmm(lin1.bias, x_a, lin1.weight.t()))
+    ones = torch.ones(N, 1, dtype=torch.float32, device=g.device)
+    dW2b = _outer_sum(gh_perm, torch.cat([a1, ones], dim=1)).index_select(0, rp.gh_col)
+    g_pre = gpre_perm.index_select(1, rp.gpre_col)
+    dW1b = _outer_sum(g_pre, torch.cat([x_a, ones], dim=1))
+    st.grads_per_step[i] = _mlp_param_grads(cparams, lin1, lin2, dW1b[:, :-1], dW1b[:, -1], dW2b[:, :-1], dW2b[:, -1])
+
+
 def _fwd_layerwise(st, step, layer, d):
     x_a = _source_rows(layer, st.cur)
     if _is_dense(layer):                    # (forward direction only: training_plan)
@@ -1202,7 +1289,7 @@ def _bwd_layerwise(st, i, layer, d):
 _STEPS = {_FOLDED: (_fwd_folded, _bwd_folded), _PERM: (_fwd_perm, _bwd_perm),
           _ELEMENTWISE: (_fwd_elementwise, _bwd_elementwise), _ELEMENTWISE_CTX: (_fwd_elementwise_ctx, _bwd_elementwise_ctx),
           _MADE: (_fwd_made, _bwd_made), _AFFINE: (_fwd_affine, _bwd_affine), _RQS: (_fwd_rqs, _bwd_rqs),
-          _WIDE: (_fwd_wide, _bwd_wide), _LAYERWISE: (_fwd_layerwise, _bwd_layerwise)}
+          _WIDE: (_fwd_wide, _bwd_wide), _LRS: (_fwd_lrs, _bwd_lrs), _LAYERWISE: (_fwd_layerwise, _bwd_layerwise)}
 
 
 class ChainFunction(torch.autograd.Function):
@@ -1234,7 +1321,8 @@ class ChainFunction(torch.autograd.Function):
                 l2vec = packs.l2_vector(fb, maps, plan.l2)
         else:
             packed = packs.pack() if packs.fused[_AFFINE] else []
-        st.packed = {_AFFINE: packed, _WIDE: packs.pack_wide() if packs.fused[_WIDE] else []}
+        st.packed = {_AFFINE: packed, _WIDE: packs.pack_wide() if packs.fused[_WIDE] else [],
+                     _LRS: packs.pack_lrs() if packs.fused[_LRS] else []}
         st.keep_graphs = any(ctx.needs_input_grad)
         if st.W != D:                # padded training layout: every kernel below sees (N, W) rows
             st.cur, st.cur_is_saved = packs.pad_rows(rows), False

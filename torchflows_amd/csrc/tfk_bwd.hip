@@ -19,6 +19,7 @@
 // is written once, coalesced.  All kernels are HBM-bound streams.
 #include "tfk_common.h"
 #include "tfk_spline.h"
+#include "tfk_lrs.h"
 
 namespace tfk {
 
@@ -1197,7 +1198,13 @@ __global__ __launch_bounds__(512) void k_rqs_coupling_train_bwd(
 
 extern "C" {
 
-int tfk_rqs_coupling_train_bwd_supported(int32_t D, int32_t n_bins) { return (D == 64 && n_bins == 8) ? 1 : 0; }
+// n_bins with bit 16 set selects the linear rational spline (tfk_lrs.hip: k_lrs_coupling_train_bwd), which exists for
+// (1 << 16) | 8 alone; every other value with a bit above the low 16 is unsupported
+int tfk_rqs_coupling_train_bwd_supported(int32_t D, int32_t n_bins)
+{
+    if (n_bins >> 16) return (D == 64 && n_bins == (kLrsTrainFlag | 8)) ? 1 : 0;
+    return (D == 64 && n_bins == 8) ? 1 : 0;
+}
 
 static int rqs_train_bwd_impl(const float *x, float *g, const float *gld, const float *params,
                               int64_t n_params, int32_t gemm2_steps, float *gh_perm, float *gpre_perm, float *hid_perm,
@@ -1209,13 +1216,18 @@ static int rqs_train_bwd_impl(const float *x, float *g, const float *gld, const 
         return fail(TFK_EINVAL, "%s: D = %d, n_bins = %d (the kernel exists for D = 64, 8 bins)", fn, D, n_bins);
     if (gemm2_steps < 1 || gemm2_steps > 4) return fail(TFK_EINVAL, "%s: GEMM-2 steps %d not in [1, 4]", fn, gemm2_steps);
     if (!(boundary > 0.0f)) return fail(TFK_EINVAL, "%s: boundary must be positive", fn);
-    const int64_t need = 8 * 64 + 16 + (int64_t)48 * gemm2_steps * 64 + 48 * 16 + 48 * 4 * 64 + 2 * 4 * 64;
+    const bool lrs = (n_bins & kLrsTrainFlag) != 0;
+    const int64_t need = lrs ? lrs_train_bwd_param_floats(gemm2_steps)
+                             : 8 * 64 + 16 + (int64_t)48 * gemm2_steps * 64 + 48 * 16 + 48 * 4 * 64 + 2 * 4 * 64;
     if (n_params != need) return fail(TFK_EINVAL, "%s: parameter block has %lld floats, expected %lld", fn,
                                       (long long)n_params, (long long)need);
     if (!x || !g || !gld || !params || !gh_perm || !gpre_perm) return fail(TFK_EINVAL, "%s: null pointer", fn);
     if (!aligned16(x) || !aligned16(g) || !aligned16(params) || !aligned16(gh_perm) || !aligned16(gpre_perm) ||
         (gscale && !aligned16(gscale)))
         return fail(TFK_EINVAL, "%s: buffers must be 16-byte aligned", fn);
+    if (lrs)
+        return lrs_train_bwd_launch(x, g, gld, params, n_params, gemm2_steps, gh_perm, gpre_perm, hid_perm, N, boundary,
+                                    inverse, gscale, g_reversed, static_cast<hipStream_t>(stream), fn);
     RqsConst C;
     C.minimum = -boundary;
     C.maximum = boundary;

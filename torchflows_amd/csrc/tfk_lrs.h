@@ -17,6 +17,18 @@ struct LrsConst {
     float c;         // log(exp(1 - 1e-5) - 1)
 };
 
+// Fused training backward of one linear-rational-spline coupling (tfk_lrs.hip: k_lrs_coupling_train_bwd; D = 64, 8 bins),
+// reached through tfk_rqs_coupling_train_bwd[_hid] with n_bins = (1 << 16) | 8 (tfk_bwd.hip validates the common arguments).
+constexpr int32_t kLrsTrainFlag = 1 << 16;
+// A1[8][64] | b1[16] | A2[64][steps2][64] | b2[64][16] | A2T[64][4][64] | A1T[2][4][64]
+constexpr int64_t lrs_train_bwd_param_floats(int32_t steps2) {
+    return 8 * 64 + 16 + (int64_t)64 * steps2 * 64 + 64 * 16 + 64 * 4 * 64 + 2 * 4 * 64;
+}
+int lrs_train_bwd_launch(const float *x, float *g, const float *gld, const float *params, int64_t n_params,
+                         int32_t gemm2_steps, float *gh_perm, float *gpre_perm, float *hid_perm, int64_t N,
+                         float boundary, int32_t inverse, const float *gscale, int32_t g_reversed, hipStream_t s,
+                         const char *fn);
+
 __device__ __forceinline__ float lrs_deriv(float u, float c) {       // linear_rational.py:79, :89
     return softplus20(c + u / 100.0f) + kLrsMinD;
 }

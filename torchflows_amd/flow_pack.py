@@ -197,7 +197,7 @@ def _bf16_pieces(w: torch.Tensor):
     """fp32 -> three bf16 pieces by truncation (hi = w & 0xffff0000, mid and lo likewise from the exact remainders),
     each returned as the int32 holding its 16 significant bits in the LOW half."""
     w = w.float().contiguous()
-    mask = torch.tensor(-65536, dtype=torch.int32, device=w.device)             # 0xffff0000
+    mask = -65536                                 # 0xffff0000 (a Python scalar: no host-to-device copy, a captured step packs too)
     hi = (w.view(torch.int32) & mask).view(torch.float32)
     r1 = w - hi
     mid = (r1.view(torch.int32) & mask).view(torch.float32)

@@ -735,6 +735,30 @@ def rqs_coupling_train_bwd(x, g, gld, params, gemm2_steps, gh_perm, gpre_perm, n
     _launch(name, g, *head, *hid, *tail)
 
 
+LRS_TRAIN_FLAG = 1 << 16      # n_bins of tfk_rqs_coupling_train_bwd[_hid] with this bit set: the linear rational spline
+
+
+def lrs_coupling_train_bwd(x, g, gld, params, gemm2_steps, gh_perm, gpre_perm, n_bins, boundary,
+                           inverse=False, gscale=None, g_reversed=False, hid_perm=None):
+    """``rqs_coupling_train_bwd`` for a linear-rational-spline coupling (csrc/tfk_lrs.hip: k_lrs_coupling_train_bwd), through
+    the same two entry points with ``LRS_TRAIN_FLAG`` set in n_bins: 32 parameters per element, so gh_perm is (N, 1024) --
+    column (8 e + c) * 16 + 4 q + r = dL/d(parameter 4 c + r of target 8 q + e) -- and ``params`` the block of include/tfk.h."""
+    name = "tfk_rqs_coupling_train_bwd" if hid_perm is None else "tfk_rqs_coupling_train_bwd_hid"
+    N, D = _rows(g, name)
+    if x.shape != g.shape or gld.numel() != N or gh_perm.shape != (N, 1024) or gpre_perm.shape != (N, 16):
+        raise NativeError(f"{name} (linear rational spline): bad x / gld / gh_perm / gpre_perm shape")
+    if hid_perm is not None and hid_perm.shape != (N, 16):
+        raise NativeError(f"{name} (linear rational spline): hid_perm must be (N, 16)")
+    if gscale is not None and gscale.numel() != D:
+        raise NativeError(f"{name}: gscale must hold D = {D} floats")
+    head = (_f32(x, name), _f32(g, name), _f32(gld, name), _f32(params, name), params.numel(),
+            int(gemm2_steps), _f32(gh_perm, name), _f32(gpre_perm, name))
+    tail = (N, D, LRS_TRAIN_FLAG | int(n_bins), C.c_float(float(boundary)), 1 if inverse else 0, _f32(gscale, name),
+            1 if g_reversed else 0)
+    hid = () if hid_perm is None else (_f32(hid_perm, name),)
+    _launch(name, g, *head, *hid, *tail)
+
+
 _rows_outer_ws = {}
 
 

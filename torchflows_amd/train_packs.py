@@ -3,6 +3,7 @@
 the rows.  The user is ``torchflows_amd/autograd.py``."""
 from __future__ import annotations
 
+import math
 from typing import List, Optional
 
 import torch
@@ -220,6 +221,171 @@ class _RqsTrainPack:
         flat = torch.cat([lin1.weight.detach().reshape(-1), lin1.bias.detach(),
                           lin2.weight.detach().reshape(-1), lin2.bias.detach(), self.zero])
         return flat[self.param_index]
+
+
+class _LrsTrainPack:
+    """Index maps between a linear-rational-spline coupling's [W1 | b1 | W2 | b2 | 0] (D = 64, 8 bins, hidden width H <= 16)
+    and the layouts of its fused training launches, built once per (H, device):
+
+    (a) ``param_index``: the operand block of tfk_rqs_coupling_train_bwd with the LRS flag (csrc/tfk_lrs.hip,
+        include/tfk.h): A1[8][64] | b1[16] | A2[64][steps2][64] | b2[64][16] | A2T[64][4][64] | A1T[2][4][64], tile 8 e + c =
+        parameters 4 c .. 4 c + 3 of the lane group's element e, in the module's own scale;
+    (b) ``fwd_index`` / ``fwd_mul`` / ``fwd_add``: the block of a one-op lean program (TFK_OP_LRS_FWD_LEAN / _INV_LEAN, bf16 x 3
+        operands, csrc/tfk_flow_rqs_chain.h) from the live weights -- ONE gather of two sources per value and
+        ((a + b / 100) * mul) + add in float64 (the log2 e, / 100, negation and c_delta terms of flow_pack._pack_lean_rqs,
+        in its order of operations), then its bf16 split: bit for bit the inference packer's block for H <= 15.  H = 16 (two
+        hidden tiles, never captured: its weight products are GEMM-library calls) goes through that packer itself;
+    (c) ``gh_col`` / ``gpre_col``: the un-permutations of the accumulator-order records;
+    (d) H <= 15: ``acc_index`` from the three tfk_rows_outer products [gh_perm^T hid_perm (1024 x 16) | x_A^T gpre_perm
+        (32 x 16) | gpre_perm^T hid_perm (16 x 16)], accumulator order, to [dW1 (H, 32) | db1 (H) | dW2 (1024, H) | db2 (1024)]."""
+
+    _cache = {}
+    N_FWD = 8 * 64 + 16 + 64 + 2 * 8 * 8 * 64 * 4          # head | A[8][8][2][64][4 dwords] (H <= 15)
+    N_EW = 2 * 64 + 4                                       # the closing TFK_OP_EW_FMA block
+
+    @classmethod
+    def get(cls, H: int, device) -> "_LrsTrainPack":
+        key = (H, str(device))
+        if key not in cls._cache:
+            cls._cache[key] = cls(H, device)
+        return cls._cache[key]
+
+    def __init__(self, H: int, device):
+        from torchflows_amd import flow_ops
+        half, EPL, P, TPE = 32, 8, 32, 8
+        self.H, self.device = H, device
+        self.steps2 = (H + 3) // 4
+        self.fwd_steps2 = (H + 1 + 3) // 4                # the lean op's: counts the bias unit (5 = two hidden tiles)
+        off_b1 = H * half
+        off_W2 = off_b1 + H
+        off_b2 = off_W2 + half * P * H
+        Z = off_b2 + half * P                             # index of the appended zero
+        self.n_flat = Z + 1
+        ar = torch.arange
+        W1idx = torch.full((16, half), Z, dtype=torch.long)
+        W1idx[:H] = ar(H)[:, None] * half + ar(half)[None, :]
+        b1idx = torch.full((16,), Z, dtype=torch.long)
+        b1idx[:H] = off_b1 + ar(H)
+        W2idx = torch.full((half, P, 16), Z, dtype=torch.long)
+        W2idx[:, :, :H] = off_W2 + ((ar(half)[:, None, None] * P + ar(P)[None, :, None]) * H + ar(H)[None, None, :])
+        b2idx = off_b2 + ar(half)[:, None] * P + ar(P)[None, :]
+        lane = ar(64)
+        ql, il = lane >> 4, lane & 15
+        unit = 4 * (il & 3) + (il >> 2)
+        q2, r2 = il >> 2, il & 3
+        qq, rr = torch.meshgrid(ar(4), ar(4), indexing="ij")
+        e_ = ar(EPL).view(EPL, 1, 1, 1)
+        c_ = ar(TPE).view(1, TPE, 1, 1)
+        k_ = ar(4).view(1, 1, 4, 1)
+        # (a) ---------------------------------------------------------------------------------------------------------
+        A1 = torch.stack([W1idx[unit, EPL * ql + s] for s in range(EPL)])
+        b1m = b1idx[4 * rr + qq]
+        # A2[e][c][r1][lane]: parameter 4 c + r2 of target 8 q2 + e, hidden unit 4 r1 + q
+        A2 = W2idx[EPL * q2.view(1, 1, 1, 64) + e_, 4 * c_ + r2.view(1, 1, 1, 64), 4 * k_ + ql.view(1, 1, 1, 64)]
+        A2 = A2[:, :, :self.steps2]
+        b2m = b2idx[EPL * qq.view(1, 1, 4, 4) + e_, 4 * c_ + rr.view(1, 1, 4, 4)]              # [e][c][q][r]
+        # A2T[e][c][r][lane]: parameter 4 c + r of target 8 q + e, hidden unit unit(i)
+        A2T = W2idx[EPL * ql.view(1, 1, 1, 64) + e_, 4 * c_ + k_, unit.view(1, 1, 1, 64)]
+        A1T = torch.stack([W1idx[4 * r + ql, EPL * (il >> 2) + 4 * t + (il & 3)] for t in range(2) for r in range(4)])
+        self.param_index = torch.cat([t.reshape(-1) for t in (A1, b1m, A2, b2m, A2T, A1T)]).to(device)
+        self.n_bwd = int(self.param_index.numel())
+        # (b) ---------------------------------------------------------------------------------------------------------
+        self.hp = half
+        self.ops = {False: flow_ops.OP_LRS_FWD_LEAN, True: flow_ops.OP_LRS_INV_LEAN}        # by "the step is an inverse"
+        self.op_ew_fma, self.fmt = flow_ops.OP_EW_FMA, flow_ops.FMT_BF16X3
+        self.c_delta = float(torch.tensor(math.log(math.exp(1 - 1e-5) - 1)))               # LinearRational.const in fp32
+        if H <= 15:
+            L2, Lg = flow_ops.LOG2E, 2.0 * flow_ops.LOG2E
+            zcol = torch.full((half, 8, 16), Z, dtype=torch.long)
+            # Q[m][p][u] = ((src_a + src_b / 100) * mul) + add, the bias of parameter p the weight of unit 15 (== 1)
+            Wb = W2idx.clone()
+            Wb[:, :, 15] = b2idx
+            Qa = torch.cat([Wb[:, 0:8], Wb[:, 0:8], Wb[:, 16:24], zcol[:, :7], Wb[:, 31:32]], dim=1)
+            Qb = torch.cat([zcol, Wb[:, 8:16], zcol, Wb[:, 24:31], zcol[:, :1]], dim=1)
+            Qmul = torch.full((half, P, 16), L2, dtype=torch.float64)
+            Qmul[:, 16:24] = -L2
+            Qadd = torch.zeros(half, P, 16, dtype=torch.float64)
+            Qadd[:, 24:31, 15] = self.c_delta * L2
+            i4 = ar(4).view(1, 1, 1, 4)
+            sel = (EPL * q2.view(1, 1, 64, 1) + ar(EPL).view(EPL, 1, 1, 1),
+                   4 * ar(TPE).view(1, TPE, 1, 1) + r2.view(1, 1, 64, 1), 4 * i4 + ql.view(1, 1, 64, 1))   # (EPL, TPE, 64, 4)
+            A1f = A1.reshape(EPL // 4, 4, 64).permute(0, 2, 1)                                 # lane-major groups of 4 k-steps
+            n_head = EPL * 64 + 16 + 2 * half
+            zero_h = torch.full((2 * half,), Z, dtype=torch.long)
+            ia = torch.cat([A1f.reshape(-1), b1m.reshape(-1), zero_h, Qa[sel].reshape(-1)])
+            ib = torch.cat([torch.full((n_head,), Z, dtype=torch.long), Qb[sel].reshape(-1)])
+            mul = torch.cat([torch.full((n_head,), Lg, dtype=torch.float64), Qmul[sel].reshape(-1)])
+            add = torch.cat([torch.zeros(EPL * 64 + 16, dtype=torch.float64), torch.ones(half, dtype=torch.float64),
+                             torch.zeros(half, dtype=torch.float64), Qadd[sel].reshape(-1)])      # pre_s = 1, pre_t = 0
+            self.n_head = n_head
+            self.fwd_index = torch.stack([ia, ib]).reshape(-1).to(device)                      # [all a | all b]
+            self.fwd_mul, self.fwd_add = mul.to(device), add.to(device)
+        # (c) column of gh_perm that holds parameter p of target m ------------------------------------------------------
+        m = ar(half)[:, None]
+        pp = ar(P)[None, :]
+        col = ((TPE * (m % EPL) + pp // 4) * 16 + 4 * (m // EPL) + pp % 4).reshape(-1)
+        self.gh_col = col.to(device)                                                        # (1024,)
+        u = ar(H)
+        self.gpre_col = (4 * (u % 4) + u // 4).to(device)                                   # (H,)
+        self.zero = torch.zeros(1, dtype=torch.float32, device=device)
+        self.ew_identity = torch.cat([torch.ones(64), torch.zeros(64 + 4)]).to(device)      # s = 1, t = 0, no log-det
+        # (d) ---------------------------------------------------------------------------------------------------------
+        GH = half * P
+        self.n_acc = GH * 16 + 32 * 16 + 16 * 16
+        if H <= 15:
+            slot = 4 * (u % 4) + u // 4                                   # column of hid_perm / gpre_perm that holds unit u
+            t1 = 4 * (col // 64) + (col % 64) % 4                         # tile and M-index of tfk_rows_outer (include/tfk.h)
+            i1 = (col % 64) // 4
+            idx1 = lambda j: ((t1 * 64 + 16 * (i1 // 4))[:, None] + j[None, :]) * 4 + (i1 % 4)[:, None]
+            dW2 = idx1(slot)                                              # (1024, H)
+            db2 = idx1(torch.tensor([15]))[:, 0]
+            e = ar(half)
+            base2 = GH * 16
+            dW1 = base2 + (((e // 16) * 64 + 16 * ((e % 16) // 4))[None, :] + slot[:, None]) * 4 + ((e % 16) % 4)[None, :]
+            base3 = base2 + 32 * 16
+            db1 = base3 + (16 * (slot // 4) + 15) * 4 + slot % 4
+            self.acc_index = torch.cat([dW1.reshape(-1), db1, dW2.reshape(-1), db2]).to(device)
+            self.acc_sizes = (H * half, H, GH * H, GH)
+            self.acc_shapes = ((H, half), (H,), (GH, H), (GH,))
+        self._rec = None
+        self._retired = []                                # (a captured step keeps the addresses of the buffers it saw)
+
+    def flat_of(self, lin1, lin2) -> List[torch.Tensor]:
+        return [lin1.weight.detach().reshape(-1), lin1.bias.detach(), lin2.weight.detach().reshape(-1),
+                lin2.bias.detach(), self.zero]
+
+    def forward_blocks(self, flats: torch.Tensor) -> torch.Tensor:
+        """(L, N_FWD) float32: the lean forward blocks of L layers of this geometry from their stacked float32
+        [W1 | b1 | W2 | b2 | 0] rows ``flats`` (L, n_flat) -- device tensor ops only, the same for every L."""
+        from torchflows_amd.flow_pack import _bf16_pieces, _bf16x3_dwords
+        L = flats.shape[0]
+        src = flats.double().index_select(1, self.fwd_index).view(L, 2, -1)
+        val = ((src[:, 0] + src[:, 1] / 100.0) * self.fwd_mul + self.fwd_add).float()
+        A3 = _bf16x3_dwords(*_bf16_pieces(val[:, self.n_head:].reshape(L, 8, 8, 1, 64, 4)), dim=4)   # (L, 8, 8, 1, 2, 64, 4)
+        return torch.cat([val[:, :self.n_head], A3.reshape(L, -1).view(torch.float32)], dim=1)
+
+    def forward_block_wide(self, lin1, lin2) -> torch.Tensor:
+        """The lean forward block of a layer of hidden width 16 (two hidden tiles): the inference packer's own."""
+        from torchflows_amd.flow_pack import _pack_lean_rqs
+        f64 = lambda t: t.detach().double()
+        one = torch.ones(self.hp, dtype=torch.float64, device=self.device)
+        return _pack_lean_rqs(self.H, 64, f64(lin1.weight), f64(lin1.bias), f64(lin2.weight).view(self.hp, 32, self.H),
+                              f64(lin2.bias).view(self.hp, 32), one, torch.zeros_like(one), self.c_delta, bf16x3=True, lrs=True)
+
+    def pack(self, lin1, lin2) -> torch.Tensor:
+        """The backward block (a) for the current weights (one layer)."""
+        return torch.cat(self.flat_of(lin1, lin2))[self.param_index]
+
+    def records(self, N: int):
+        """(gh_perm (N, 1024), gpre_perm, hid_perm (N, 16)): views of buffers that only ever grow, and are never freed."""
+        if self._rec is None or self._rec[0] < N:
+            if self._rec is not None:
+                self._retired.append(self._rec)
+            cap = max(N, 2 * self._rec[0] if self._rec is not None else N)
+            mk = lambda w: torch.empty(cap, w, dtype=torch.float32, device=self.device)
+            self._rec = (cap, mk(1024), mk(16), mk(16))
+        _, gh, gpre, hid = self._rec
+        return gh[:N], gpre[:N], hid[:N]
 
 
 class _WideTrainPack:
